@@ -42,6 +42,9 @@ Prints ONE JSON line on rank 0 with the fields the driver expects plus
                   5 / 50 / 95 % bands -- as one fused call (total_ms; no_profile_total_ms) and as separate calls (outside the
                   timed region).
   --fp32 adds the config-5 report: the fp32-arithmetic reduced-QoI kernel against the fp64 one on identical inputs.
+  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (at most 64 MB: beyond that a fixed, seeded
+                  sample of the samples) and lists the files in config.dump_outputs.  The inputs are seeded (--seed) and the
+                  timed steps meet the batches in the same order in every run, so two builds can be compared file for file.
 """
 import argparse
 import json
@@ -373,6 +376,37 @@ def fp32_report(n, seed):
     return compare_with_fp64(n, lambda batch: synth_inputs(batch, seed, 0))
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def sample_outputs(arrays, n, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs, on the device: `arrays` maps a name to a tensor whose rows are k x n samples (k > 1 for the QoIs
+    gathered from every rank, rank-major).  When the arrays would exceed `limit` bytes as float64 (float32 where the tensor
+    is fp32) the same fixed, seeded sample of the n sample indices is kept in every array (and in every rank's part).
+    Returns ({name: device tensor}, rows kept per part)."""
+    import numpy as np
+    import torch
+    out_dtype = {name: torch.float32 if a.dtype in (torch.float32, torch.uint8, torch.bool) else torch.float64 for name, a in arrays.items()}
+    row_bytes = sum((a.shape[0] // n) * (a[0].numel() if a.dim() > 1 else 1) * out_dtype[name].itemsize for name, a in arrays.items())
+    m = min(n, (limit - 1024 * len(arrays)) // row_bytes)              # (1 KB per file for the .npy header)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+    snap = {}
+    for name, a in arrays.items():
+        k = a.shape[0] // n
+        idx = torch.as_tensor((np.arange(k)[:, None] * n + rows[None, :]).ravel(), device=a.device)
+        snap[name] = a.index_select(0, idx).to(out_dtype[name])
+    return snap, int(m)
+
+
+def write_outputs(out_dir, snap):
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in snap.items():
+        np.save(d / f'{name}.npy', t.cpu().numpy())
+    return sorted(f'{name}.npy' for name in snap)
+
+
 def spawn_ranks(args_list, n):
     """`bench.py --gpus N` outside torch.distributed.run: start the N ranks as a child process (nothing in THIS process
     has touched the GPU) and pass its stdout -- the one JSON line of rank 0 -- and exit code through."""
@@ -439,7 +473,13 @@ def main():
     ap.add_argument('--dist-backend', default='nccl', help='nccl (= RCCL; default) or gloo (rehearsal on one GPU)')
     ap.add_argument('--oversubscribe', action='store_true',
                     help='rehearsal only: allow more ranks than GPUs (ranks then share devices; never a measurement)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed -- V_cc, div_angle, T_c, j_ion, invalid; at N > 1 '
+                         'rank 0\'s, except what the exchange gathers from every rank (the QoIs; j_ion with --gather full) -- as '
+                         'DIR/<name>.npy, float64 (float32 for an fp32 profile and the flags); beyond 64 MB, a fixed seeded sample of the samples')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(sys.argv[1:], args.gpus))
@@ -613,11 +653,24 @@ def main():
                 flag = torch.tensor([1 if done else 0], dtype=torch.int64, device=batch.device)
                 dist.all_reduce(flag, op=dist.ReduceOp.MIN)          # every rank takes the same number of steps
                 done = bool(flag.item())
-            if done or spin_steps >= 4096:
+            # (a whole number of rotations, so that the timed steps meet the batches in the same order in every run)
+            if (done or spin_steps >= 4096) and spin_steps % nb == 0:
                 break
     for _ in range(args.warmup):
         step()
     elapsed = timed(args.steps)
+    # --dump-outputs: what the last timed step left for its caller, sampled on the device now (the steps below overwrite it)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        last = batches[(counter[0] - 1) % nb]
+        qoi = last.qoi
+        if pipe is not None and full_recv is None:      # the pipeline's steps write the QoIs into its own buffers
+            qoi = pipe.assemble() if pipe.gather else pipe.assemble()[:, :n]   # (gathered: every rank's, as received)
+        arrays = {'V_cc': qoi[0], 'div_angle': qoi[1], 'T_c': qoi[2]}
+        if last.profile:
+            arrays['j_ion'] = full_recv if full_recv is not None else last.j_ion
+        arrays['invalid'] = last.invalid
+        dump = sample_outputs(arrays, n)
     # the same steps with every launch waiting for the one before (what rounds 1-2 timed), for the record
     elapsed_one_stream = None
     if side is not None and not multi:
@@ -785,6 +838,13 @@ def main():
                          'write_stream_GBs': write_stream,
                          'frac_of_write_stream': (achieved / write_stream) if write_stream else None},
         }
+        if dump is not None:
+            snap, rows = dump
+            line['config']['dump_outputs'] = {'dir': str(args.dump_outputs), 'files': write_outputs(args.dump_outputs, snap),
+                                              'samples_kept': rows, 'samples_per_rank': n,
+                                              'note': 'outputs of the last timed step; a sample of them (numpy default_rng(0), sorted) when '
+                                                      'samples_kept < samples_per_rank'}
+            del snap, dump
         if world == 1 and not multi and args.full_config_samples > 0 and not (args.no_profile or args.mixed):
             del batch, batches, b
             torch.cuda.empty_cache()

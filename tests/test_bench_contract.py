@@ -104,6 +104,30 @@ def test_single_gpu_line_carries_the_whole_config():
         assert 0.3 < line['roofline']['frac_traced'] < 1.0 and 'kernel_srchash' in line['roofline']['frac_traced_source']
 
 
+def test_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the outputs of the last timed step as DIR/<name>.npy, at most 64 MB (here a seeded sample of the
+    131072 samples), identical in two runs with the same arguments -- also with a rotation of 6 batches, which the clock
+    spin-up's steps of 8 do not divide."""
+    import numpy as np
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        out = subprocess.run([sys.executable, str(ROOT / 'bench.py'), *SMALL, '--no-cpu-baseline', '--no-single-batch', '--batches', '6',
+                              '--dump-outputs', str(d)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(_one_json_line(out.stdout))
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob('*.npy'))})
+        assert sum(f.stat().st_size for f in d.glob('*.npy')) <= 64_000_000
+    info = lines[0]['config']['dump_outputs']
+    assert sorted(dumps[0]) == ['T_c', 'V_cc', 'div_angle', 'invalid', 'j_ion'] and info['files'] == [f'{k}.npy' for k in sorted(dumps[0])]
+    m = info['samples_kept']
+    assert 0 < m < 131072 == info['samples_per_rank'] and lines[0]['steps'] == 4
+    assert dumps[0]['j_ion'].shape == (m, 91) and dumps[0]['j_ion'].dtype == np.float64 and dumps[0]['V_cc'].shape == (m,)
+    assert dumps[0]['invalid'].dtype == np.float32 and np.isfinite(dumps[0]['V_cc']).any()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+
+
 def test_two_ranks_through_torch_distributed_run():
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))

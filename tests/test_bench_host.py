@@ -32,3 +32,25 @@ def test_counter_traffic_is_replayed_only_for_the_kernel_sources_in_the_tree(tmp
     monkeypatch.undo()
     real = bench.read_committed_traffic(1_250_000, 'tile')
     assert real[0] is None or 0.95 * 872 * 1_250_000 < real[0] < 1.1 * 872 * 1_250_000
+
+
+def test_dump_sample_is_fixed_and_fits_the_limit():
+    """--dump-outputs: beyond the byte limit the same seeded rows are kept in every array and in every rank's part of a gathered
+    array; fp32 / flag arrays are written as float32, the rest as float64.  CPU tensors stand in for device ones."""
+    import numpy as np
+    import torch
+    import bench
+    n, world = 1000, 2
+    arrays = {'V_cc': torch.arange(world * n, dtype=torch.float64), 'j_ion': torch.arange(n * 91, dtype=torch.float32).reshape(n, 91),
+              'invalid': (torch.arange(n) % 3 == 0).to(torch.uint8)}
+    limit = 20_000 + 1024 * len(arrays)
+    snap, m = bench.sample_outputs(arrays, n, limit=limit)
+    assert m == 20_000 // (world * 8 + 91 * 4 + 4) and sum(t.numel() * t.element_size() for t in snap.values()) <= limit
+    rows = snap['j_ion'][:, 0].numpy().astype(np.int64) // 91
+    assert np.all(np.diff(rows) > 0) and np.array_equal(snap['V_cc'].numpy(), np.concatenate([rows, n + rows]).astype(np.float64))
+    assert np.array_equal(snap['invalid'].numpy(), (rows % 3 == 0).astype(np.float32))
+    assert {k: t.dtype for k, t in snap.items()} == {'V_cc': torch.float64, 'j_ion': torch.float32, 'invalid': torch.float32}
+    again, _ = bench.sample_outputs(arrays, n, limit=limit)
+    assert all(torch.equal(again[k], snap[k]) for k in snap)
+    whole, m_all = bench.sample_outputs(arrays, n)                      # under the limit: every sample, in order
+    assert m_all == n and torch.equal(whole['V_cc'], arrays['V_cc']) and torch.equal(whole['j_ion'], arrays['j_ion'])
