@@ -70,8 +70,10 @@ def column_percentiles(a, percentiles):
     q = gamma
     a = a.double()
     # a (n, m) view whose columns are contiguous arrays -- e.g. `batch.qoi.T`, the [3][n] reduced-QoI tensor seen as (n, 3) --
-    # is read in place (`pem_quantiles_strided_f64_dev`): the three scalar QoIs of a campaign in ONE selection, without a copy
-    transposed = a.dim() == 2 and a.shape[1] > 1 and a.stride(0) == 1 and a.stride(1) >= n
+    # is read in place (`pem_quantiles_strided_f64_dev`): the three scalar QoIs of a campaign in ONE selection, without a copy.
+    # A column stride of 1 is the row form whatever n is (a (1, m) row seen through `.T` has strides (1, 1)): the column form
+    # needs a stride of at least two
+    transposed = a.dim() == 2 and a.shape[1] > 1 and a.stride(0) == 1 and a.stride(1) >= max(n, 2)
     flat = a if transposed else a.reshape(n, -1)
     if not transposed and not flat.is_contiguous():
         flat = flat.contiguous()
@@ -351,8 +353,6 @@ def forward_uq_statistics(n: int, seed: int = 0, keep_profile: bool = True, perc
     design = sampling.Design(priors=priors, seed=seed)
     batch = CoupledBatch(n, device=device, profile=keep_profile)
     pct = [25.0, 75.0] + [float(x) for x in percentiles]
-    if len(pct) > MAX_Q:
-        raise ValueError(f'at most {MAX_Q - 2} percentiles besides the quartiles')
     answered, premasked, qj, qs, certain, uncertain = False, False, None, None, None, None
     thresh = int(0.75 * _lib.NANGLE)
     nv, cap = len(QOI_NAMES), 65536
@@ -366,6 +366,8 @@ def forward_uq_statistics(n: int, seed: int = 0, keep_profile: bool = True, perc
         open_rows = torch.empty(cap, dtype=torch.int64, device=dev)
         open_count = torch.zeros(1, dtype=torch.int32, device=dev)
         if fused and n >= FUSED_STATS_MIN_N:
+            if len(pct) > MAX_Q:              # (one counting launch selects them all; the passes below take any number)
+                raise ValueError(f'the fused campaign takes at most {MAX_Q - 2} percentiles besides the quartiles')
             rp, rn, gm = _linear_ranks(n, pct)
             qj = torch.empty((len(pct), _lib.NANGLE), dtype=torch.float64, device=dev)
             # (the scalar QoIs' percentiles are selected by the same call, on a second stream, while the profile's records are sorted)

@@ -154,6 +154,52 @@ def test_fused_monte_carlo_equals_sample_then_evaluate():
         assert float(((quiet.qoi - ref.qoi).abs() / ref.qoi.abs().clamp_min(1e-300)).max()) < 1e-11
 
 
+def _same(a, b):
+    """equal value for value, NaN where the other is NaN (torch.equal says False for any NaN)"""
+    return a.shape == b.shape and bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+
+
+@pytest.mark.gpu
+def test_fused_monte_carlo_under_wide_priors_equals_sample_then_evaluate_and_the_oracle():
+    """pem_coupled_mc_f64_dev on priors that reach the fuzz regimes (negative amplitudes, narrow beams, zero CEX cross-section,
+    negative flow rates; NORMAL and LOGUNIFORM dimensions): the fused launch equals Design.fill + run in full, reduced and
+    tile-layout form, for ragged tiles, first indices above 2^32 and every kind of Saltelli block; the inputs it writes are
+    held to the oracle sample by sample under the fuzz tool's per-entry bounds."""
+    from hallthrusterpem_amd import constants
+    from hallthrusterpem_amd.batch import CoupledBatch
+    from hallthrusterpem_amd.models.coupled import COUPLED_INPUTS
+    from hallthrusterpem_amd.sampling import Design
+    from wild_parity import check_against_oracle, wide_priors
+    design = Design(priors=wide_priors(), seed=77, stream=4)
+    n_invalid = n_nonfinite = 0
+    for n, first, swap in ((5_037, 0, -1), (2_561, 2 ** 32 + 12_345, 7), (3_001, 2 ** 33 + 1, 0), (2_000, 99, 14), (1_000, 5, -2)):
+        ref = CoupledBatch(n)
+        design.fill(ref.inputs, first_index=first, swap_dim=swap)
+        ref.run()
+        fused = CoupledBatch(n)
+        fused.inputs.zero_()
+        fused.run_mc(design, first_index=first, write_inputs=True, swap_dim=swap)
+        tile = CoupledBatch(n, layout='tile')
+        tile.run_mc(design, first_index=first, swap_dim=swap)
+        quiet = CoupledBatch(n, profile=False)
+        quiet.run_mc(design, first_index=first, swap_dim=swap)
+        plain = CoupledBatch(n, profile=False)
+        plain.inputs.copy_(ref.inputs)
+        plain.run()
+        torch.cuda.synchronize()
+        assert torch.equal(fused.inputs, ref.inputs), (n, swap)
+        for k in ('V_cc', 'div_angle', 'T_c', 'I_B0', 'T', 'j_ion', 'invalid'):
+            assert _same(fused.outputs()[k], ref.outputs()[k]), (n, swap, k)
+            assert _same(tile.outputs()[k], ref.outputs()[k]), (n, swap, k, 'tile')
+        assert _same(quiet.qoi, plain.qoi) and torch.equal(quiet.invalid, plain.invalid), (n, swap)
+        x = {k: ref.inputs[i].cpu().numpy() for i, k in enumerate(COUPLED_INPUTS)}
+        got = {k: v.cpu().numpy() for k, v in ref.outputs().items()}
+        check_against_oracle(x, got, constants.TORR_2_PA, f'(wide priors, n {n}, swap {swap})')
+        n_invalid += int(got['invalid'].sum())
+        n_nonfinite += int((~np.isfinite(got['T_c'])).sum())
+    assert n_invalid > 100 and n_nonfinite > 10, (n_invalid, n_nonfinite)      # the priors do reach the regimes
+
+
 @pytest.mark.gpu
 def test_rejection_of_plume_spikes():
     from hallthrusterpem_amd.models.plume import current_density

@@ -645,3 +645,91 @@ def test_two_host_threads_run_campaigns_at_once():
     for seed in (31, 32):
         assert got[seed][0] is True
         assert np.array_equal(got[seed][1], want[seed][0]) and np.array_equal(got[seed][2], want[seed][1]), seed
+
+
+def _numpy_masks_and_bands(got, prof, pct):
+    """filter_outputs' numpy branch and np.percentile on host copies of a campaign's outputs and profile"""
+    from hallthrusterpem_amd import drivers
+    host = {k: got[k].cpu().numpy() for k in ('V_cc', 'div_angle', 'T_c')}
+    host['j_ion'] = prof
+    nan_idx, outlier_idx = drivers.filter_outputs(host)
+    with np.errstate(invalid='ignore'):
+        bands = {k: np.percentile(v, pct, axis=0) for k, v in host.items()}
+    return nan_idx, outlier_idx, bands
+
+
+@pytest.mark.parametrize('negative_density', [False, True])
+def test_fused_campaign_statistics_under_wide_priors_equal_numpy(negative_density):
+    """forward_uq_statistics (the counting instantiation of the tile kernel, JMODE 4 / 5) on priors that reach the fuzz regimes,
+    profile kept and not: QoIs, invalid flags, I_B0 and T equal forward_uq's; bands equal np.percentile of the profile, NaN
+    columns included; masks equal filter_outputs' numpy branch.  With a negative density (c4 < 0: exp(+x) overflows, fuzz seed
+    53) the profile holds non-finite values, which make the on-chip selection decline -- and the answer is still numpy's."""
+    import torch
+    from hallthrusterpem_amd import drivers
+    from wild_parity import wide_priors
+    n, seed, pct = 60_000, 31, [5.0, 50.0, 95.0]
+    pri = wide_priors(negative_density)
+    ref = drivers.forward_uq(n, seed=seed, priors=pri, keep_profile=True, keep_inputs=False)
+    red = drivers.forward_uq(n, seed=seed, priors=pri, keep_profile=False, keep_inputs=False)
+    prof = ref['j_ion'].cpu().numpy()
+    assert not np.isfinite(prof).all() and float(ref['invalid'].float().mean()) > 0.1
+    for keep in (True, False):
+        got = drivers.forward_uq_statistics(n, seed=seed, priors=pri, keep_profile=keep, percentiles=pct)
+        nan_w, outl_w, bands_w = _numpy_masks_and_bands(got, prof, pct)
+        print(f'\nwide priors (negative density {negative_density}), keep_profile {keep}: '
+              f'{"answered on chip" if got["fused"] else "declined"}, premasked {got["premasked"]}')
+        assert got['fused'] is False                        # (a non-finite profile value: the selection declines)
+        for k in ('V_cc', 'div_angle', 'T_c', 'I_B0', 'T', 'invalid'):
+            # the counting launch integrates the profile as the profile mode does; a declined call without a profile may
+            # have taken the reduced-QoI launch instead
+            assert _same(got[k], ref[k]) or (not keep and _same(got[k], red[k])), (k, keep)
+        if keep:
+            assert _same(got['j_ion'], ref['j_ion'])
+        for k in ('V_cc', 'div_angle', 'T_c', 'j_ion'):
+            assert np.array_equal(got['bands'][k].cpu().numpy(), bands_w[k], equal_nan=True), (k, keep)
+            assert np.array_equal(got['nan_idx'][k].cpu().numpy(), nan_w[k]), (k, keep)
+            assert np.array_equal(got['outlier_idx'][k].cpu().numpy(), outl_w[k]), (k, keep)
+    assert np.isnan(bands_w['j_ion']).any() and bool(nan_w['j_ion'].any())
+
+
+def _same(a, b):
+    import torch
+    return a.shape == b.shape and bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+
+
+def test_column_percentiles_of_one_and_two_row_views_through_a_transpose():
+    """(1, m) and (2, m) views made with `.T` -- a (1, m) view of an (m, 1) column has strides (1, 1), the row form whatever n is,
+    not the column form (which needs a column stride of at least two) -- against np.percentile."""
+    import torch
+    from hallthrusterpem_amd.drivers import column_percentiles
+    rng = np.random.default_rng(3)
+    for m in (1, 2, 3, 91, 300):
+        for rows in (1, 2):
+            base = torch.from_numpy(rng.standard_normal((m, rows))).cuda()
+            view = base.T                                        # (rows, m), strides (1, rows)
+            wide = torch.from_numpy(rng.standard_normal((m, rows + 3))).cuda()[:, :rows].T      # strides (1, rows + 3)
+            for v in (view, wide):
+                want = np.percentile(v.cpu().numpy(), [25.0, 50.0, 75.0, 5.0, 95.0, 0.0, 100.0], axis=0)
+                got = column_percentiles(v, [25.0, 50.0, 75.0, 5.0, 95.0, 0.0, 100.0]).cpu().numpy()
+                assert np.array_equal(got, want), (m, rows, tuple(v.stride()))
+                assert np.array_equal(column_percentiles(v, 50.0).cpu().numpy(), np.percentile(v.cpu().numpy(), 50.0, axis=0))
+
+
+def test_campaign_statistics_take_any_number_of_percentiles_outside_the_fused_launch():
+    """forward_uq_statistics: the limit of one counting launch (MAX_Q - 2 percentiles besides the quartiles) applies to the fused
+    launch only; with fused=False, or fewer samples than it takes, seven percentiles are numpy's.  The fused launch still says no."""
+    from hallthrusterpem_amd import drivers
+    pct = [1.0, 5.0, 25.0, 50.0, 75.0, 95.0, 99.0]
+    for n, fused in ((20_000, False), (drivers.FUSED_STATS_MIN_N - 1, True)):
+        for keep in (True, False):
+            got = drivers.forward_uq_statistics(n, seed=9, keep_profile=keep, percentiles=pct, fused=fused)
+            ref = drivers.forward_uq(n, seed=9, keep_profile=True, keep_inputs=False)
+            assert got['fused'] is False
+            prof = ref['j_ion'].cpu().numpy()
+            nan_w, outl_w, bands_w = _numpy_masks_and_bands(got, prof, pct)
+            for k in ('V_cc', 'div_angle', 'T_c', 'j_ion'):
+                assert got['bands'][k].shape[0] == len(pct)
+                assert np.array_equal(got['bands'][k].cpu().numpy(), bands_w[k]), (k, n, keep)
+                assert np.array_equal(got['nan_idx'][k].cpu().numpy(), nan_w[k]) and np.array_equal(got['outlier_idx'][k].cpu().numpy(), outl_w[k])
+    with pytest.raises(ValueError):
+        drivers.forward_uq_statistics(drivers.FUSED_STATS_MIN_N, seed=9, percentiles=pct)
