@@ -43,24 +43,29 @@ static_assert(MAXA == 5 && PEM_SURR_MAX_LEVEL == 4, "the kernel nests four outer
 
 __device__ __forceinline__ int nodes_of(int level) { return level == 0 ? 1 : (1 << level) + 1; }
 
-// Chebyshev-Lobatto nodes -cos(pi j / (m - 1)) of levels 1..4, concatenated (offsets 0, 3, 8, 17), and the Lagrange
-// denominators c_j = 1 / prod_{i != j} (t_j - t_i) OF THESE DOUBLES (exact rational arithmetic, then rounded)
+// Chebyshev-Lobatto nodes of levels 1..4, concatenated (offsets 0, 3, 8, 17): the CORRECTLY ROUNDED doubles of -cos(pi j / (m - 1)),
+// the same doubles as surrogate.nodes() that the model is evaluated at (so that the interpolant goes through its training values
+// exactly).  Correct rounding makes them nested across levels and antisymmetric.  And the Lagrange denominators
+// c_j = 1 / prod_{i != j} (t_j - t_i) OF THESE DOUBLES (exact rational arithmetic, then rounded to nearest).
+// tests/test_surrogate_nodes.py parses both tables and checks them.
 __device__ const double LOBATTO_NODES[34] = {
-    -1.0, 0.0, 1.0,
-    -1.0, -0.70710678118654752440, 0.0, 0.70710678118654752440, 1.0,
-    -1.0, -0.92387953251128675613, -0.70710678118654752440, -0.38268343236508977173, 0.0,
-    0.38268343236508977173, 0.70710678118654752440, 0.92387953251128675613, 1.0,
-    -1.0, -0.9807852804032304, -0.9238795325112867, -0.8314696123025452, -0.7071067811865476, -0.5555702330196023, -0.38268343236508984,
-    -0.19509032201612833, 0.0, 0.19509032201612833, 0.38268343236508984, 0.5555702330196023, 0.7071067811865476, 0.8314696123025452,
-    0.9238795325112867, 0.9807852804032304, 1.0};
+    -0x1.0000000000000p+0, 0.0, 0x1.0000000000000p+0,
+    -0x1.0000000000000p+0, -0x1.6a09e667f3bcdp-1, 0.0, 0x1.6a09e667f3bcdp-1, 0x1.0000000000000p+0,
+    -0x1.0000000000000p+0, -0x1.d906bcf328d46p-1, -0x1.6a09e667f3bcdp-1, -0x1.87de2a6aea963p-2, 0.0,
+    0x1.87de2a6aea963p-2, 0x1.6a09e667f3bcdp-1, 0x1.d906bcf328d46p-1, 0x1.0000000000000p+0,
+    -0x1.0000000000000p+0, -0x1.f6297cff75cb0p-1, -0x1.d906bcf328d46p-1, -0x1.a9b66290ea1a3p-1, -0x1.6a09e667f3bcdp-1,
+    -0x1.1c73b39ae68c8p-1, -0x1.87de2a6aea963p-2, -0x1.8f8b83c69a60bp-3, 0.0, 0x1.8f8b83c69a60bp-3, 0x1.87de2a6aea963p-2,
+    0x1.1c73b39ae68c8p-1, 0x1.6a09e667f3bcdp-1, 0x1.a9b66290ea1a3p-1, 0x1.d906bcf328d46p-1, 0x1.f6297cff75cb0p-1,
+    0x1.0000000000000p+0};
 __device__ const double LOBATTO_INVDEN[34] = {
     0x1.0000000000000p-1, -0x1.0000000000000p+0, 0x1.0000000000000p-1,
     0x1.0000000000001p+0, -0x1.0000000000000p+1, 0x1.fffffffffffffp+0, -0x1.0000000000000p+1, 0x1.0000000000001p+0,
     0x1.fffffffffffffp+2, -0x1.0000000000001p+4, 0x1.0000000000001p+4, -0x1.fffffffffffffp+3, 0x1.fffffffffffffp+3,
     -0x1.fffffffffffffp+3, 0x1.0000000000001p+4, -0x1.0000000000001p+4, 0x1.fffffffffffffp+2,
-    0x1.ffffffffffff8p+9, -0x1.ffffffffffffep+10, 0x1.0000000000003p+11, -0x1.0000000000005p+11, 0x1.0000000000003p+11, -0x1.0000000000001p+11,
-    0x1.ffffffffffffdp+10, -0x1.ffffffffffff7p+10, 0x1.ffffffffffff4p+10, -0x1.ffffffffffff7p+10, 0x1.ffffffffffffdp+10, -0x1.0000000000001p+11,
-    0x1.0000000000003p+11, -0x1.0000000000005p+11, 0x1.0000000000003p+11, -0x1.ffffffffffffep+10, 0x1.ffffffffffff8p+9};
+    0x1.ffffffffffff6p+9, -0x1.ffffffffffffcp+10, 0x1.0000000000002p+11, -0x1.0000000000003p+11, 0x1.fffffffffffffp+10,
+    -0x1.fffffffffffffp+10, 0x1.0000000000001p+11, -0x1.0000000000000p+11, 0x1.0000000000000p+11, -0x1.0000000000000p+11,
+    0x1.0000000000001p+11, -0x1.fffffffffffffp+10, 0x1.fffffffffffffp+10, -0x1.0000000000003p+11, 0x1.0000000000002p+11,
+    -0x1.ffffffffffffcp+10, 0x1.ffffffffffff6p+9};
 
 // Lagrange basis of the M Chebyshev-Lobatto nodes at t, product form
 template <int M>

@@ -84,7 +84,8 @@ __global__ __launch_bounds__(BLOCK) void svd_compress_kernel(long long n, int do
     constexpr int KG = 64 / ROWS;                            // k-groups: lane (row, grp) takes k = grp, grp + KG, ...
     const int ksteps = (dof + KG - 1) / KG;
     double* basis_p = lds;                                   // [ksteps*KG][16]
-    const int tile_doubles = (ROWS * dof + KG + 1) & ~1;
+    // the tile is reused for the ROWS x r latents it becomes: with r > dof (small dof on the tiled path) they need more room
+    const int tile_doubles = ((ROWS * dof + KG > ROWS * r ? ROWS * dof + KG : ROWS * r) + 1) & ~1;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     double* tile = lds + ksteps * KG * 16 + wave * tile_doubles;  // [ROWS][dof] + slack
     double* logtab = lds + ksteps * KG * 16 + WAVES * tile_doubles;  // log10 mode: 16 KB table behind the tiles
@@ -450,7 +451,8 @@ int pem_svd_compress_f64_dev(size_t n, int dof, int rank, int norm, double norm_
     // ROWS samples per tile: 16 (4 k-groups) for dof <= 96, 8 (8 k-groups) above; UN: 16-byte pieces per lane of a tile
     // (12 covers 16 x 96, 13 covers 8 x 208); RT: latent columns computed (>= rank)
     const int rows = dof <= 96 ? 16 : 8, kg = 64 / rows;
-    const size_t lds = ((size_t)((dof + kg - 1) / kg) * kg * 16 + (size_t)WAVES * ((rows * dof + kg + 1) & ~1) +
+    const int tile_doubles = ((rows * dof + kg > rows * rank ? rows * dof + kg : rows * rank) + 1) & ~1;     // as in the kernel
+    const size_t lds = ((size_t)((dof + kg - 1) / kg) * kg * 16 + (size_t)WAVES * tile_doubles +
                         (norm == PEM_NORM_LOG10 ? (size_t)pem::LOG_TABLE_DOUBLES : 0)) * 8;
     const size_t tiles = (n + rows - 1) / rows;
     size_t blocks = balanced_blocks((tiles + WAVES - 1) / WAVES, 256 * 2);

@@ -41,13 +41,24 @@ MAX_LEVEL = 4       # include/pem_hip.h PEM_SURR_MAX_LEVEL
 FIELDS = {'j_ion': _lib.NANGLE}     # field outputs the surrogate can carry as SVD latents: name -> degrees of freedom
 
 
+# the 17 Chebyshev-Lobatto nodes of level 4, -cos(pi j / 16), CORRECTLY ROUNDED to double.  Every lower level is a subset of
+# them (nested grids share their node doubles) and the set is antisymmetric.  csrc/pem_surrogate.hip's LOBATTO_NODES holds the
+# same doubles: the interpolant the kernel evaluates goes through the values the model was evaluated at, exactly
+# (tests/test_surrogate_nodes.py checks both against a multiple-precision cosine)
+LOBATTO17 = tuple(float.fromhex(h) for h in (
+    '-0x1.0000000000000p+0', '-0x1.f6297cff75cb0p-1', '-0x1.d906bcf328d46p-1', '-0x1.a9b66290ea1a3p-1', '-0x1.6a09e667f3bcdp-1',
+    '-0x1.1c73b39ae68c8p-1', '-0x1.87de2a6aea963p-2', '-0x1.8f8b83c69a60bp-3', '0x0.0p+0', '0x1.8f8b83c69a60bp-3',
+    '0x1.87de2a6aea963p-2', '0x1.1c73b39ae68c8p-1', '0x1.6a09e667f3bcdp-1', '0x1.a9b66290ea1a3p-1', '0x1.d906bcf328d46p-1',
+    '0x1.f6297cff75cb0p-1', '0x1.0000000000000p+0'))
+
+
 def nodes(level: int) -> np.ndarray:
+    """the 2^level + 1 nodes -cos(pi j / 2^level) of a level >= 1 (correctly rounded), the single node 0 of level 0"""
     if level == 0:
         return np.zeros(1)
-    m = 2 ** level + 1
-    x = -np.cos(np.pi * np.arange(m) / (m - 1))
-    x[(m - 1) // 2] = 0.0                      # exact centre node (cos(pi/2) is 6e-17 in floating point)
-    return x
+    if not 1 <= level <= MAX_LEVEL:
+        raise ValueError(f'levels 0..{MAX_LEVEL}')
+    return np.array(LOBATTO17[::1 << (MAX_LEVEL - level)])
 
 
 class SparseGridSurrogate:

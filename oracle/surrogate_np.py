@@ -6,12 +6,14 @@ import numpy as np
 
 
 def nodes(level):
+    """-cos(pi j / (m - 1)), j = 0..m-1, correctly rounded to double (a 300-bit cosine, then one rounding): the node doubles of
+    the kernel and of the surrogate's training grid"""
     if level == 0:
         return np.zeros(1)
+    import mpmath
     m = 2 ** level + 1
-    x = -np.cos(np.pi * np.arange(m) / (m - 1))
-    x[(m - 1) // 2] = 0.0
-    return x
+    with mpmath.workprec(300):
+        return np.array([float(-mpmath.cospi(mpmath.mpf(j) / (m - 1))) + 0.0 for j in range(m)])
 
 
 def lagrange_basis(level, t):
