@@ -16,6 +16,8 @@ LIB_PATH = PKG / 'libpem_hip.so'
 PEM_OK, PEM_ERR_INVALID_ARG, PEM_ERR_HIP, PEM_ERR_NO_DEVICE = 0, 1, 2, 3
 NANGLE = 91
 FUSED_LATENT_MAX_RANK = 8     # PEM_FUSED_LATENT_MAX_RANK (include/pem_hip.h): latents the fused model -> compression launch keeps
+FUSED_SYSTEM_MAX_RECORDS = 1024   # PEM_FUSED_SYSTEM_MAX_RECORDS: records (and conditions) of the fused multi-QoI likelihood's LDS table
+SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of that table
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -45,6 +47,8 @@ SIGNATURES = {
     'pem_coupled_tiled_f64_dev': (C.c_int, [_sz, _f8, _f8, _dp] + [_dp] * 7 + [_dp]),
     'pem_coupled_mixed_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [_dp] * 7 + [_dp]),
     'pem_coupled_loglik_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int] + [_dp] * 4 + [_dp] * 5 + [_dp]),
+    'pem_coupled_system_loglik_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int]
+                                          + [_dp] * 5 + [_dp]),
     'pem_coupled_latent_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp] + [_dp] * 4 + [_dp]),
     'pem_loglik_marginal_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, _f8, _f8, _dp, _dp, _dp]),
     'pem_log_prior_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),

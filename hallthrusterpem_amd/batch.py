@@ -173,6 +173,29 @@ class CoupledBatch:
         _lib.check(rc)
         return out
 
+    def run_system_loglik(self, likelihood, out=None, stream=None):
+        """Coupled evaluation + the multi-QoI log-likelihood of a `likelihood.SystemLikelihood` in one launch
+        (`pem_coupled_system_loglik_f64_dev`): the j_ion records are reduced against the profile in LDS, the V_cc, T and u_ion
+        records in the per-sample epilogue.  Sample i belongs to condition i mod n_cond.  Returns the (n,) per-sample sums;
+        V_cc / div_angle / T_c / invalid are written as by `run`."""
+        import torch
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        if self.layout != 'soa':
+            raise NotImplementedError("the fused likelihood launch reads SoA inputs: use layout='soa'")
+        lk = likelihood
+        if lk.sweep_radius != self.radius:
+            raise ValueError(f'the likelihood\'s j_ion data are at r = {lk.sweep_radius}, the batch sweeps r = {self.radius}')
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())                                   # noqa: E731
+        z0, z1, ncells = lk.uion_grid
+        rc = _lib.load().pem_coupled_system_loglik_f64_dev(
+            self.n, constants.TORR_2_PA, self.radius, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
+            p(lk.node), z0, z1, ncells, p(self.qoi[0]), p(self.qoi[1]), p(self.qoi[2]), p(out), p(self.invalid),
+            C.c_void_p(s.cuda_stream))
+        _lib.check(rc)
+        return out
+
     def run_latent(self, compression, out=None, stream=None):
         """Coupled evaluation + `compression.SVDCompression.compress(j_ion)` in one launch
         (`pem_coupled_latent_f64_dev`): the latents are accumulated in the registers of the angle loop, the profile is

@@ -18,6 +18,10 @@ The reference scripts are stale and untested, its sampler (`mcmciterators` DRAM)
 absent: parity UNPINNED.  The likelihood is checked against the oracle + numpy (tests/test_calibration.py); the
 discharge current of the analytic thruster test double is I_d = I_B0 / (1 - 2 a_1) (tests/sim_hallthruster.jl:35-48;
 its `c1` is the anomalous-transport coefficient, PEM variable `a_1`).
+
+`SystemPosterior` is the same flow for the reference's `System` calibration (mcmc.py:28-45, QOIS = V_cc, T, uion, jion): each
+quantity from its own dataset at its own operating conditions (`likelihood.SystemLikelihood`), all compared in ONE fused launch
+(`pem_coupled_system_loglik_f64_dev`), so that the cathode parameters are constrained by data as well as the plume's.
 """
 import ctypes as C
 import math
@@ -26,7 +30,7 @@ import numpy as np
 
 from . import _lib
 from .batch import CoupledBatch
-from .likelihood import JionLikelihood
+from .likelihood import JionLikelihood, SystemLikelihood
 from .models.coupled import COUPLED_INPUTS
 from .sampling import LOGUNIFORM, NORMAL, PEM_V0_PRIORS, UNIFORM, Design
 
@@ -61,16 +65,12 @@ def log_prior(theta, names, priors=None):
     return total
 
 
-class JionPosterior:
-    def __init__(self, theta_names, operating, alpha, y, std, n_chains: int, n_nuisance: int = 100, priors=None,
-                 seed: int = 0, discharge=(4.5, 0.2), sweep_radius: float = 1.0, fresh_nuisance: bool = True,
-                 device=None):
-        """theta_names: calibrated inputs (subset of the 15 coupled inputs, not operating ones);
-        operating: (Ne, 3) array of `P_b [Torr], V_a [V], mdot_a [kg/s]` per experiment;
-        alpha, y, std: (Ne, Na) measurement angles [rad], current densities and standard deviations at `sweep_radius`;
-        discharge: (I_d, sigma) of the extra discharge-current weight (mcmc.py:48-49,102-104) or None;
-        fresh_nuisance: new nuisance draws on every evaluation (as the reference) -- inside a captured graph the
-        draws are whatever was recorded (common random numbers)."""
+class BatchedPosterior:
+    """What the posteriors of this module share: K chains x M nuisance draws x Ne operating conditions in one `CoupledBatch`,
+    the prior on the device, marginalisation, graph capture.  A subclass builds its likelihood and runs it (`_run_loglik`)."""
+
+    def _setup(self, theta_names, operating, make_likelihood, n_chains, n_nuisance, priors, seed, discharge, sweep_radius,
+               fresh_nuisance):
         import torch
         self.names = tuple(theta_names)
         for k in self.names:
@@ -81,7 +81,7 @@ class JionPosterior:
         if op.shape[1] != len(OPERATING):
             raise ValueError('operating conditions are rows of (P_b, V_a, mdot_a)')
         self.priors = PEM_V0_PRIORS if priors is None else priors
-        self.lik = JionLikelihood(alpha, y, std, device=device)
+        self.lik = make_likelihood()
         if self.lik.n_cond != self.Ne:
             raise ValueError('one row of measurements per operating condition')
         self.n = self.K * self.M * self.Ne
@@ -107,6 +107,9 @@ class JionPosterior:
         self._b = np.ascontiguousarray([q.b for q in pr], dtype=np.float64)
         self._lp = torch.empty(self.K, dtype=torch.float64, device=self.device)
         self._out = torch.empty(self.K, dtype=torch.float64, device=self.device)
+
+    def _run_loglik(self):
+        raise NotImplementedError
 
     # ------------------------------------------------------------------------------------------------ evaluation
     def assemble_inputs(self, theta):
@@ -135,7 +138,7 @@ class JionPosterior:
         import torch
         assert theta.shape == (self.K, len(self.names)) and theta.dtype == torch.float64 and theta.device == self.device
         self.assemble_inputs(theta)
-        self.batch.run_loglik(self.lik, out=self.loglik)
+        self._run_loglik()
         return self._marginal(None, torch.empty_like(self._out) if out is None else out)
 
     def log_prior(self, theta, out=None):
@@ -158,7 +161,7 @@ class JionPosterior:
         assert theta.shape == (self.K, len(self.names)) and theta.dtype == torch.float64 and theta.device == self.device
         self.log_prior(theta, out=self._lp)
         self.assemble_inputs(theta)
-        self.batch.run_loglik(self.lik, out=self.loglik)
+        self._run_loglik()
         return self._marginal(self._lp, torch.empty_like(self._out) if out is None else out)
 
     # ---------------------------------------------------------------------------------------------- graph capture
@@ -179,6 +182,41 @@ class JionPosterior:
             return out
         replay.graph, replay.theta, replay.out = graph, static_theta, out
         return replay
+
+
+class JionPosterior(BatchedPosterior):
+    def __init__(self, theta_names, operating, alpha, y, std, n_chains: int, n_nuisance: int = 100, priors=None,
+                 seed: int = 0, discharge=(4.5, 0.2), sweep_radius: float = 1.0, fresh_nuisance: bool = True,
+                 device=None):
+        """theta_names: calibrated inputs (subset of the 15 coupled inputs, not operating ones);
+        operating: (Ne, 3) array of `P_b [Torr], V_a [V], mdot_a [kg/s]` per experiment;
+        alpha, y, std: (Ne, Na) measurement angles [rad], current densities and standard deviations at `sweep_radius`;
+        discharge: (I_d, sigma) of the extra discharge-current weight (mcmc.py:48-49,102-104) or None;
+        fresh_nuisance: new nuisance draws on every evaluation (as the reference) -- inside a captured graph the
+        draws are whatever was recorded (common random numbers)."""
+        self._setup(theta_names, operating, lambda: JionLikelihood(alpha, y, std, device=device), n_chains, n_nuisance, priors,
+                    seed, discharge, sweep_radius, fresh_nuisance)
+
+    def _run_loglik(self):
+        self.batch.run_loglik(self.lik, out=self.loglik)
+
+
+class SystemPosterior(BatchedPosterior):
+    def __init__(self, theta_names, likelihood: SystemLikelihood, n_chains: int, n_nuisance: int = 100, priors=None,
+                 seed: int = 0, discharge=(4.5, 0.2), fresh_nuisance: bool = True):
+        """The posterior of the reference's `System` calibration (mcmc.py:28-130): V_cc, thrust, ion velocity and ion current
+        density, each from its own dataset (`likelihood.SystemLikelihood`, whose conditions are the Ne operating conditions
+        here), evaluated by ONE fused launch (`pem_coupled_system_loglik_f64_dev`) per evaluation.  The interface of
+        `JionPosterior`; theta_names, n_chains, n_nuisance, priors, seed, fresh_nuisance as there.
+        discharge: (I_d, sigma) of the discharge-current weight added for every condition, or None; dropped when the
+        likelihood's component is 'Cathode' (mcmc.py:100-101)."""
+        if not likelihood.use_discharge:
+            discharge = None
+        self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, priors, seed, discharge,
+                    likelihood.sweep_radius, fresh_nuisance)
+
+    def _run_loglik(self):
+        self.batch.run_system_loglik(self.lik, out=self.loglik)
 
 
 def capture_graph(body, device, warmup: int = 2, generator=None):
@@ -210,7 +248,7 @@ class Metropolis:
     theta' = theta + scale * N(0, I) with a per-parameter `scale`; the nuisance draws inside the posterior are the
     recorded ones (common random numbers), i.e. the chain targets the M-sample marginal likelihood estimate."""
 
-    def __init__(self, posterior: JionPosterior, theta0, scale, seed: int = 0, use_graph: bool = True):
+    def __init__(self, posterior: BatchedPosterior, theta0, scale, seed: int = 0, use_graph: bool = True):
         import torch
         self.post = posterior
         dev = posterior.device
@@ -277,7 +315,8 @@ class DRAM:
       adaptation  after `adapt_after` steps, every `adapt_interval` steps: C = (2.4^2 / d) (cov(chain so far) + eps I), from a
                 running mean / scatter matrix per chain (Welford)
 
-    `log_posterior(theta[K, d]) -> logp[K]` is any callable on torch tensors (a `JionPosterior.log_posterior`, or a closed
+    `log_posterior(theta[K, d]) -> logp[K]` is any callable on torch tensors (a `JionPosterior` / `SystemPosterior`
+    `.log_posterior`, or a closed
     form on the CPU in the tests).  Both stages are evaluated for all chains every step (a fixed launch sequence: with
     `use_graph` the step is one hipGraph replay, as `Metropolis`); the adaptation runs between replays and updates `L` in place."""
 

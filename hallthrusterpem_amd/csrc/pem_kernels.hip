@@ -107,6 +107,19 @@ struct McDesign {
     unsigned long long ld;
 };
 
+// fused multi-QoI likelihood mode (JMODE 6): the ragged measurement table, copied into LDS at kernel start.  Records are
+// 32 bytes {w, y, 1/std, bits} (pem_hip.h, pem_coupled_system_loglik_f64_dev): j_ion {w, y, 1/std, k}, u_ion {w, y, 1/std, p},
+// V_cc and T {0, y, 1/std, 0}; span[c][kind] = {first record, count} of condition c, kinds PEM_SYS_* (j_ion, V_cc, T, u_ion);
+// node[p] = a grid index of u_ion, whose denominator 1 + exp(-100 (z - 0.04)) is evaluated once per workgroup.
+struct SystemTable {
+    const double* rec;
+    const int32_t* span;
+    const int32_t* node;
+    int n_rec, n_node;
+    double z0, z1;
+    int ncells;
+};
+
 // the per-sample inputs of one lane, prefetched one tile ahead
 template <bool COUPLED>
 struct SampleIn {
@@ -214,6 +227,8 @@ __device__ __forceinline__ SampleIn<true> generate_sample(const McDesign& mc, co
 //            csrc/pem_latent.hip)
 //            4: as 1, and the staged profile is COUNTED against the brackets of a percentile selection on its way out (count_round);
 //            5: the same without the stores -- the percentiles of a profile that is never written
+//            6: fused multi-QoI likelihood -- JMODE 3's j_ion records against the staged profile, plus V_cc, thrust and u_ion
+//               records of the sample's condition in the epilogue (system_epilogue_sum)
 // LDS map (doubles): shared by the workgroup: simpson[96][2] | dpoly[32*12];  per wave: params[NROWS][64] |
 // tile[S*91] | 2 (sink).  The Simpson table is padded with zero weights to L*CH <= 96 entries so the angle loop
 // needs no branch.  The den/num partial sums of a round reuse the rows of `params` that the round has consumed.
@@ -228,7 +243,7 @@ constexpr int QPOLY_DOUBLES = (PEM_NDI + PEM_NQB) * PEM_NDC * 2;
 template <int L, int JMODE>
 constexpr int wave_lds_doubles() {
     return param_rows<L>() * WAVE +
-           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
+           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5 || JMODE == 6) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
 }
 template <int L, int JMODE>
 constexpr int fast_lds_doubles() { return TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>(); }
@@ -264,6 +279,9 @@ __device__ __forceinline__ void stream_store(f64x2 v, f64x2* dst) {
 // LDS views of one wave
 struct WaveLds {
     const double* meas;      // fused likelihood: [n_cond*n_ang] records {weight, y, inv_std, k (integer bits)}, or nullptr
+    const int2* span;        // JMODE 6: [n_cond][4] {first record, count} of each kind (meas holds the records)
+    const double* unode;     // JMODE 6: [max(n_node, 2)] u_ion denominators 1 + exp(-100 (z_k - 0.04))
+    int n_unode;
     const double2* simpson;  // [96] {cden, cnum}
     const double* poly;      // [32*12]
     const double2* qpoly;    // reduced-QoI mode: [(32+64)*12] {Qd, Qn} coefficients of the Simpson functionals, or nullptr
@@ -509,6 +527,66 @@ __device__ PEM_COUNT_LINKAGE unsigned count_round(unsigned ctx_off, unsigned til
     return cnt;
 }
 
+// Fused likelihood modes (JMODE 3 / 6): lane c's share -- records c, c+L, ... -- of the n_rec j_ion records {weight, y, 1/std, k}
+// of one sample against its staged profile row; the L chunk lanes of the sample are summed by the caller.
+template <int L, typename JT>
+__device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec, const JT* row, int c) {
+    double acc = 0.0;
+    constexpr int MU = PEM_LOGLIK_MU;   // records in flight per lane: the k -> row[k] chain is two LDS latencies deep
+    for (int a0 = c; a0 < n_rec; a0 += MU * L) {
+        double4 e[MU];
+        double lo_v[MU], hi_v[MU];
+#pragma unroll
+        for (int u = 0; u < MU; ++u) e[u] = mt[a0 + u * L < n_rec ? a0 + u * L : a0];
+#pragma unroll
+        for (int u = 0; u < MU; ++u) {
+            const int k = __double_as_longlong(e[u].w) & 0x7f;
+            lo_v[u] = row[k];
+            hi_v[u] = row[k + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < MU; ++u) {
+            const double model = fma(e[u].x, hi_v[u] - lo_v[u], lo_v[u]);
+            const double z = (e[u].y - model) * e[u].z;
+            if (a0 + u * L < n_rec) acc = fma(-0.5 * z, z, acc);
+        }
+    }
+    return acc;
+}
+
+// u_ion grid node c of sim_hallthruster.jl:46-47, z = range(z0, z1, length = ncells), and the denominator of u_ion there:
+// one expression for thruster_uion_kernel and the fused multi-QoI mode, so that both see the same node values
+__device__ __forceinline__ double uion_z(double z0, double z1, int ncells, int c) {
+    return z0 + (z1 - z0) * ((double)c / (double)(ncells - 1));
+}
+__device__ __forceinline__ double uion_den(double z) { return 1.0 + exp(-100.0 * (z - 0.04)); }
+
+// JMODE 6 epilogue, one lane per sample: the V_cc, thrust and u_ion records of condition `cond` added to `ll` (the sample's j_ion
+// sum).  A kind without records adds nothing -- whatever that part of the model is (a NaN v_exh of V_cc > V_a included).
+__device__ __forceinline__ double system_epilogue_sum(double ll, const WaveLds& m, unsigned cond, double V_cc,
+                                                      double thrust, double v_exh) {
+    const double4* rec = reinterpret_cast<const double4*>(m.meas);
+    const int2* sp = m.span + 4 * cond;
+    const int2 rv = sp[PEM_SYS_VCC], rt = sp[PEM_SYS_T], ru = sp[PEM_SYS_UION];
+    for (int i = rv.x; i < rv.x + rv.y; ++i) {   // the clipped cathode coupling voltage
+        const double z = (rec[i].y - V_cc) * rec[i].z;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    for (int i = rt.x; i < rt.x + rt.y; ++i) {   // the thruster's thrust T (not the plume's T_c)
+        const double z = (rec[i].y - thrust) * rec[i].z;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    const unsigned pmax = (unsigned)(m.n_unode < 2 ? 0 : m.n_unode - 2);
+    for (int i = ru.x; i < ru.x + ru.y; ++i) {   // u_ion at nodes p, p+1 of the record, interpolated linearly (np.interp)
+        const double4 e = rec[i];
+        const unsigned p = min((unsigned)__double_as_longlong(e.w), pmax);
+        const double u0 = v_exh / m.unode[p], u1 = v_exh / m.unode[p + 1];
+        const double z = (e.y - fma(e.x, u1 - u0, u0)) * e.z;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    return ll;
+}
+
 // One 64-sample tile.  FULL = every sample of the tile exists (the steady state of the persistent loop:
 // no bounds checks and a fixed number of stores, so the compiler can count them); FULL = false is the
 // ragged last tile of a batch.
@@ -533,13 +611,14 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     const bool live = FULL || g < io.n;
 
     // ------------------------------ PRELUDE: one lane per sample ------------------------------
-    double I_B0, thrust = 0.0, V_cc = 0.0;
+    double I_B0, thrust = 0.0, V_cc = 0.0, v_exh = 0.0;
     bool have_T;
     if constexpr (COUPLED) {
         V_cc = cathode_vcc(in.P_b, in.x0, in.x1, in.x2, in.x3, in.x4, io.torr2pa);
         const ThrusterQoI th = thruster_stage(in.x0, V_cc, in.x5, in.x6);
         I_B0 = th.I_B0;
         thrust = th.T;
+        v_exh = th.v_exh;
         have_T = true;
     } else {
         I_B0 = in.x0;
@@ -694,32 +773,19 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
                 }
                 wave_lds_sync();
                 const long long first = t * WAVE + (long long)round * S;
-                if constexpr (JMODE == 3) {
-                    static_assert(JMODE != 3 || 2 * L < param_rows<L>(), "row 2L of `params` carries the likelihood sum");
+                if constexpr (JMODE == 3 || JMODE == 6) {
+                    static_assert(2 * L < param_rows<L>(), "row 2L of `params` carries the likelihood sum");
                     // measured current densities against the staged profile: lane (s, c) takes measurements c, c+L, ...
                     // of its sample's condition (sample index mod n_cond); the sample's sum goes to row 2L of `params`
                     const unsigned cond = ((unsigned)((t * WAVE) % io.n_cond) + (unsigned)(round * S + s)) % (unsigned)io.n_cond;
-                    const double4* mt = reinterpret_cast<const double4*>(m.meas) + cond * (io.n_ang | 1);   // {weight, y, 1/std, k}
                     const JT* row = tile + s * NANG;
-                    double acc = 0.0;
-                    constexpr int MU = PEM_LOGLIK_MU;   // records in flight per lane: the k -> row[k] chain is two LDS latencies deep
-                    for (int a0 = c; a0 < io.n_ang; a0 += MU * L) {
-                        double4 e[MU];
-                        double lo_v[MU], hi_v[MU];
-#pragma unroll
-                        for (int u = 0; u < MU; ++u) e[u] = mt[a0 + u * L < io.n_ang ? a0 + u * L : a0];
-#pragma unroll
-                        for (int u = 0; u < MU; ++u) {
-                            const int k = __double_as_longlong(e[u].w) & 0x7f;
-                            lo_v[u] = row[k];
-                            hi_v[u] = row[k + 1];
-                        }
-#pragma unroll
-                        for (int u = 0; u < MU; ++u) {
-                            const double model = fma(e[u].x, hi_v[u] - lo_v[u], lo_v[u]);
-                            const double z = (e[u].y - model) * e[u].z;
-                            if (a0 + u * L < io.n_ang) acc = fma(-0.5 * z, z, acc);
-                        }
+                    double acc;
+                    if constexpr (JMODE == 3) {
+                        const double4* mt = reinterpret_cast<const double4*>(m.meas) + cond * (io.n_ang | 1);   // {weight, y, 1/std, k}
+                        acc = jion_records_sum<L>(mt, io.n_ang, row, c);
+                    } else {
+                        const int2 sp = m.span[4 * cond + PEM_SYS_JION];
+                        acc = jion_records_sum<L>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c);
                     }
 #pragma unroll
                     for (int sh = S; sh < WAVE; sh <<= 1) acc += __shfl_xor(acc, sh);   // the L chunk lanes of sample s
@@ -792,6 +858,12 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     if constexpr (JMODE == 3) {
         if (live) io.loglik[g] = params[(2 * L) * WAVE + lane];
     }
+    if constexpr (JMODE == 6) {
+        if (live) {
+            const unsigned cond = ((unsigned)((t * WAVE) % io.n_cond) + (unsigned)lane) % (unsigned)io.n_cond;
+            io.loglik[g] = system_epilogue_sum(params[(2 * L) * WAVE + lane], m, cond, V_cc, thrust, v_exh);
+        }
+    }
     if (live) {
         stream_store1(acos(cos_div), io.div + g);
         if (have_T) stream_store1(thrust * cos_div, io.Tc + g);
@@ -812,10 +884,11 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
 template <int JMODE, bool MC>
 constexpr int min_waves_per_simd() { return (MC && JMODE == 0) ? 3 : 1; }
 
-// Only the fused Monte-Carlo instantiations carry the ~340-byte design in their kernel arguments.
+// Only the fused Monte-Carlo instantiations carry the ~340-byte design in their kernel arguments, and only the fused multi-QoI
+// likelihood mode its measurement table.
 struct NoDesign {};
-template <bool MC>
-using DesignArg = typename std::conditional<MC, McDesign, NoDesign>::type;
+template <bool MC, int JMODE = 0>
+using DesignArg = typename std::conditional<MC, McDesign, typename std::conditional<JMODE == 6, SystemTable, NoDesign>::type>::type;
 
 // bytes of LDS the counting modes add per workgroup: brackets' {loh, words} [91][NQ] | below counters [NQ][91] | premask thresholds [91] x 16
 template <int NQ, bool PM>
@@ -823,7 +896,7 @@ constexpr int count_lds_bytes() { return NANG * NQ * 8 + NQ * NANG * 4 + 8 + (PM
 
 template <int L, bool COUPLED, int JMODE, bool MC = false, int NQ = 0, bool PM = false>
 __global__ __launch_bounds__(WAVE * WPB) __attribute__((amdgpu_waves_per_eu(min_waves_per_simd<JMODE, MC>())))
-void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC> mc) {
+void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, JMODE> mc) {
     static_assert(!MC || COUPLED, "the fused Monte-Carlo mode generates the coupled inputs");
     static_assert((JMODE == 4 || JMODE == 5) == (NQ > 0), "the counting modes, and only they, know their number of brackets");
     static_assert(NQ == 0 || L == 4, "count_round keeps one bit per sample of a 16-sample round");
@@ -868,6 +941,26 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC> 
             meas[r + 3] = __longlong_as_double((long long)io.m_kidx[i]);
         }
         m.meas = meas;
+    }
+    m.span = nullptr;
+    m.unode = nullptr;
+    m.n_unode = 0;
+    if constexpr (JMODE == 6) {   // records | spans | u_ion denominators behind the per-wave regions (layout: system_lds_bytes)
+        double* meas = lds + TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>();
+        for (int i = tid; i < 4 * mc.n_rec; i += WAVE * WPB) meas[i] = mc.rec[i];
+        int2* span = reinterpret_cast<int2*>(meas + 4 * mc.n_rec);
+        for (int i = tid; i < 4 * io.n_cond; i += WAVE * WPB) {   // clamped into the table: a span never reads past it
+            const int first = min(max(mc.span[2 * i], 0), mc.n_rec);
+            span[i] = make_int2(first, min(max(mc.span[2 * i + 1], 0), mc.n_rec - first));
+        }
+        double* unode = reinterpret_cast<double*>(span + 4 * io.n_cond);
+        for (int i = tid; i < (mc.n_node > 2 ? mc.n_node : 2); i += WAVE * WPB)
+            unode[i] = i < mc.n_node ? uion_den(uion_z(mc.z0, mc.z1, mc.ncells, min(max(mc.node[i], 0), mc.ncells - 1)))
+                                     : __builtin_nan("");
+        m.meas = meas;
+        m.span = span;
+        m.unode = unode;
+        m.n_unode = mc.n_node;
     }
 
     using QC = typename std::conditional<(NQ > 0), QCount, NoCount>::type;
@@ -1724,9 +1817,9 @@ __global__ __launch_bounds__(BLOCK) void thruster_uion_kernel(long long n, const
     for (long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x; idx < total; idx += stride) {
         const long long i = idx / ncells;
         const int c = (int)(idx - i * ncells);
-        const double z = z0 + (z1 - z0) * ((double)c / (double)(ncells - 1));
+        const double z = uion_z(z0, z1, ncells, c);
         if (i == 0 && z_out) z_out[c] = z;
-        u_ion[idx] = v_exh[i] / (1.0 + exp(-100.0 * (z - 0.04)));
+        u_ion[idx] = v_exh[i] / uion_den(z);
     }
 }
 
@@ -1863,6 +1956,11 @@ int fast_grid(long long per_cu, long long ntiles, bool memory_bound, unsigned* g
     return PEM_OK;
 }
 
+// JMODE 6's table in LDS: records [n_rec][4] doubles | spans [n_cond][4] int2 | u_ion denominators [max(n_node, 2)] doubles
+size_t system_lds_bytes(int n_cond, const SystemTable& tab) {
+    return (size_t)tab.n_rec * 32 + (size_t)n_cond * 32 + (size_t)(tab.n_node > 2 ? tab.n_node : 2) * 8;
+}
+
 template <int L, int JMODE, bool MC, int NQ = 0, bool PM = false>
 size_t r1_lds_bytes(const PlumeIO& io) {
     size_t lds = (size_t)fast_lds_doubles<L, JMODE>() * 8;
@@ -1906,8 +2004,10 @@ int r1_per_cu(size_t lds, long long* per_cu) {
 
 // `grid_only`: report the grid the launch would use (the counting modes size their record buffer by it) and launch nothing
 template <int L, bool COUPLED, int JMODE, bool MC = false, int NQ = 0, bool PM = false>
-int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McDesign& mc = McDesign{}, unsigned* grid_only = nullptr) {
-    const size_t lds = r1_lds_bytes<L, JMODE, MC, NQ, PM>(io);
+int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McDesign& mc = McDesign{}, unsigned* grid_only = nullptr,
+              const SystemTable* sys = nullptr) {
+    size_t lds = r1_lds_bytes<L, JMODE, MC, NQ, PM>(io);
+    if constexpr (JMODE == 6) lds += system_lds_bytes(io.n_cond, *sys);
     const long long ntiles = (io.n + WAVE - 1) / WAVE;
     unsigned grid = 0;
     auto kern = plume_r1_kernel<L, COUPLED, JMODE, MC, NQ, PM>;
@@ -1924,6 +2024,7 @@ int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McD
         return PEM_OK;
     }
     if constexpr (MC) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, mc);
+    else if constexpr (JMODE == 6) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *sys);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, NoDesign{});
     HIP_TRY(hipGetLastError());
     return PEM_OK;
@@ -2734,6 +2835,32 @@ int pem_coupled_loglik_f64_dev(size_t n, double torr2pa, double radius, const do
                kidx, weight, y, inv_std, loglik, n_cond, n_ang};
     CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
     return launch_r1<4, true, 3>(io, cio, static_cast<hipStream_t>(stream));
+}
+
+// ---- coupled + multi-QoI likelihood fused: j_ion against the staged profile, V_cc / T / u_ion in the epilogue ----------
+int pem_coupled_system_loglik_f64_dev(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a,
+                                      const double* T_e, const double* V_vac, const double* Pstar, const double* P_T,
+                                      const double* mdot_a, const double* a_1, const double* c0, const double* c1, const double* c2,
+                                      const double* c3, const double* c4, const double* c5, const double* sigma_cex, int n_cond,
+                                      int n_rec, const double* rec, const int32_t* span, int n_node, const int32_t* node, double z0,
+                                      double z1, int ncells, double* V_cc, double* div_angle, double* T_c, double* loglik,
+                                      uint8_t* invalid, pem_stream_t stream) {
+    if (n_cond < 1 || n_cond > PEM_FUSED_SYSTEM_MAX_RECORDS || n_rec < 0 || n_rec > PEM_FUSED_SYSTEM_MAX_RECORDS || n_node < 0 ||
+        n_node > 2 * PEM_FUSED_SYSTEM_MAX_RECORDS)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_loglik: 1 <= n_cond <= %d, 0 <= n_rec <= %d, 0 <= n_node <= %d "
+                    "(PEM_FUSED_SYSTEM_MAX_RECORDS)", PEM_FUSED_SYSTEM_MAX_RECORDS, PEM_FUSED_SYSTEM_MAX_RECORDS,
+                    2 * PEM_FUSED_SYSTEM_MAX_RECORDS);
+    if (n_node > 0 && ncells < 2) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_loglik: need at least 2 u_ion grid points");
+    if (n == 0) return PEM_OK;
+    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !mdot_a || !a_1 || !c0 || !c1 || !c2 || !c3 || !c4 || !c5 ||
+        !sigma_cex || (n_rec > 0 && !rec) || !span || (n_node > 0 && !node) || !V_cc || !div_angle || !T_c || !loglik)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_loglik: NULL array");
+    if (int rc = check_device()) return rc;
+    PlumeIO io{(long long)n, torr2pa, radius, P_b, c0, c1, c2, c3, c4, c5, sigma_cex, nullptr, nullptr, nullptr, div_angle, T_c, invalid, nullptr,
+               nullptr, nullptr, nullptr, nullptr, loglik, n_cond, 0};
+    CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
+    const SystemTable tab{rec, span, node, n_rec, n_node, z0, z1, ncells};
+    return launch_r1<4, true, 6>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, &tab);
 }
 
 // ---- coupled, mixed precision: fp64 arithmetic, the 91-point profile stored as fp32 -----------------

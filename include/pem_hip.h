@@ -220,6 +220,36 @@ int pem_coupled_loglik_f64_dev(size_t n, double torr2pa, double radius, const do
                                const double* weight, const double* y, const double* inv_std, double* V_cc,
                                double* div_angle, double* T_c, double* loglik, uint8_t* invalid, pem_stream_t stream);
 
+/* pem_coupled_f64_dev + the Gaussian log-likelihood of several measured quantities in one launch -- the `System` calibration of
+ * the reference (scripts/pem_v0/mcmc.py:28-45,57-104, QOIS = V_cc, T, uion, jion; its driver layer is stale and third-party:
+ * parity UNPINNED, held to the oracle + numpy).  Sample i belongs to condition i mod n_cond; loglik[i] is the sum over that
+ * condition's records of -0.5 z^2, z = (y - model) / std:
+ *   PEM_SYS_JION  {w, y, 1/std, k}  model = fma(w, j[k+1] - j[k], j[k]) on the 91-point profile (k an int64 bit pattern < 90):
+ *                                   pem_coupled_loglik_f64_dev's term, on the profile staged in LDS
+ *   PEM_SYS_VCC   {0, y, 1/std, 0}  model = the clipped cathode coupling voltage V_cc
+ *   PEM_SYS_T     {0, y, 1/std, 0}  model = the thruster test double's thrust T (not the plume's T_c)
+ *   PEM_SYS_UION  {w, y, 1/std, p}  model = fma(w, u(z_b) - u(z_a), u(z_a)), a = node[p], b = node[p+1] (p an int64 bit pattern),
+ *                                   u(z) = v_exh / (1 + exp(-100 (z - 0.04))) on z_c = z0 + (z1 - z0) (c / (ncells - 1)): the node
+ *                                   values of pem_thruster_uion_f64_dev, bit for bit
+ * rec: [n_rec][4] doubles; span: [n_cond][4 kinds][2] int32 {first record, count} (kinds in the order above); node: [n_node]
+ * int32 grid indices.  A condition without records of a kind adds exactly 0 for it, whatever that part of the model is.
+ * The j_ion records of a sample are summed by 4 lanes against the staged profile, the others by one lane in the epilogue;
+ * with j_ion records only, loglik equals pem_coupled_loglik_f64_dev's bit for bit.  The whole table is staged in LDS:
+ * n_cond, n_rec <= PEM_FUSED_SYSTEM_MAX_RECORDS, n_node <= 2 PEM_FUSED_SYSTEM_MAX_RECORDS.  V_cc, div_angle, T_c, invalid
+ * (optional) as pem_coupled_loglik_f64_dev.  Marginalise with pem_loglik_marginal_f64_dev ([n_chains][n_draws][n_cond]).   */
+#define PEM_FUSED_SYSTEM_MAX_RECORDS 1024
+#define PEM_SYS_JION 0
+#define PEM_SYS_VCC 1
+#define PEM_SYS_T 2
+#define PEM_SYS_UION 3
+int pem_coupled_system_loglik_f64_dev(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a,
+                                      const double* T_e, const double* V_vac, const double* Pstar, const double* P_T,
+                                      const double* mdot_a, const double* a_1, const double* c0, const double* c1,
+                                      const double* c2, const double* c3, const double* c4, const double* c5,
+                                      const double* sigma_cex, int n_cond, int n_rec, const double* rec, const int32_t* span,
+                                      int n_node, const int32_t* node, double z0, double z1, int ncells, double* V_cc,
+                                      double* div_angle, double* T_c, double* loglik, uint8_t* invalid, pem_stream_t stream);
+
 /* pem_coupled_f64_dev + pem_svd_compress_f64_dev in one launch: latent[i][r] = sum_k norm(j_ion[i][k]) basis[k][r]
  * accumulated in the registers of the angle loop, one lane per sample (csrc/pem_latent.hip) -- the profile is neither
  * stored nor staged (120 + 24 + 8 rank bytes per evaluation).  norm: PEM_NORM_NONE or PEM_NORM_LOG10; basis: [91][rank] device array, rank <=
