@@ -60,6 +60,8 @@ SIGNATURES = {
     'pem_sparse_grid_values_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp, _sz, C.c_int, C.c_int, _dp]),
     'pem_sparse_predict_field_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp, _sz, C.c_int, C.c_int,
                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp]),
+    'pem_sparse_predict_chain_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, _dp, _f8, _f8, _f8, _f8, _dp, _sz, _dp, _sz,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp]),
     'pem_key_minmax_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, _dp, _dp, _dp]),
     'pem_range_hist_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_range_narrow_dev': (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
@@ -88,6 +90,13 @@ SIGNATURES = {
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),
 }
+
+
+class SurrStage(C.Structure):
+    """pem_surr_stage (include/pem_hip.h): one table of the chained predict; an array of three is passed by pointer"""
+    _fields_ = [('index', _dp), ('coef', _dp), ('values', _dp), ('n_beta', C.c_int), ('n_out', C.c_int), ('max_active', C.c_int),
+                ('max_level', C.c_int)]
+
 
 _lib = None
 _hip_runtime = None

@@ -27,6 +27,7 @@
 //   * only the two outer dimensions' bases go through LDS: 36 KB + coordinates per workgroup instead of 55 KB.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 #include "pem_common.h"
@@ -195,6 +196,7 @@ __global__ __launch_bounds__(BLOCK) void sparse_predict_kernel(long long n, int 
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) acc[o] = 0.0;
         for (int bi = 0; bi < n_beta; ++bi) {
+            // (this grid step has a twin, grid_term below, used by the chain kernel: a change here is made there too)
             const int32_t* e = index + (size_t)bi * IDX_STRIDE;
             const int na = e[0];
             const double* val = values + (size_t)e[1] * n_out;
@@ -236,6 +238,7 @@ __global__ __launch_bounds__(BLOCK) void sparse_predict_kernel(long long n, int 
                 if (EXACT || o < n_out) out[(size_t)o * ld_out + i] = acc[o];
         }
         if (rc.field) {
+            // (twin: rebuild_field below, used by the chain kernel: a change here is made there too)
             // the latents of this workgroup's 256 points through LDS (the basis slots are free again), then every WAVE rebuilds the
             // dof values of its 64 points row by row: lane = field index, 512 contiguous bytes per store
             __syncthreads();                                 // (another wave may still read its basis slots)
@@ -285,6 +288,154 @@ void launch_predict(size_t n, int n_dim, int n_beta, const int32_t* index, const
                        index, coef, values, n_out, t, ld, out, ld_out, per_grid, max_outer, max_m, basis_words, rc);
 }
 
+// ---- the component chain (round 5): cathode -> V_cc -> thruster -> I_B0 -> plume, three tables in ONE launch --------------------
+// scripts/pem_v0/pem_v0_SPT-100.yml:4-6,55-63,110-178,215-280: the reference trains one surrogate per component and chains them
+// through the coupling variables.  The helpers below are the single-table kernel's per-grid and field-rebuild steps, restated for
+// the chain's stages: sparse_predict_kernel keeps its own inline copies so that none of its instantiations changes (calling these
+// helpers from it, even __forceinline__, reorders its registers and instructions: its assembly is no longer the same), so a fix to
+// one copy is made to the other by hand -- both are marked.  Both call
+// stage_basis / contract_grid, so a stage sums in the single-table kernel's order and the chain equals three single-table
+// launches bit for bit.
+// One grid of a table: stage the outer dimensions' bases of this thread's point (coordinates in `coord`, [dims][BLOCK]) in its
+// LDS slots under `basis` (max_outer slots of ostride doubles) and add the grid's interpolant, weighted by *cb, to acc.
+// twin of the per-grid step inside sparse_predict_kernel's loop over the grids
+template <int NOUT, bool EXACT>
+__device__ __forceinline__ void grid_term(const int32_t* __restrict__ e, const double* __restrict__ values, int n_out, const double* cb,
+                                          const double* coord, double* basis, int tid, int max_outer, int ostride, double (&acc)[NOUT]) {
+    const int na = e[0];
+    const double* val = values + (size_t)e[1] * n_out;
+    // right-align the active dimensions: (1, .., 1, m) / (1, .., m, m') / ... gives the same node order (a dimension with one
+    // node contributes no stride), and the innermost -- unrolled -- one is always an active one.  The outer dimensions' LDS
+    // slots are right-aligned inside the max_outer slots the launch has room for.
+    const int sh = MAXA - na;
+    int m[MAXO];
+    const double* slots = basis + tid - (MAXO - max_outer) * ostride;     // slot a of this thread (only active ones are touched)
+#pragma unroll
+    for (int a = 0; a < MAXO; ++a) {
+        const bool on = a >= sh;
+        m[a] = on ? nodes_of(e[2 + MAXA + (on ? a - sh : 0)]) : 1;
+        // (this thread's slots only: no barrier, a wave's LDS traffic is executed in order)
+        if (on) stage_basis(coord[e[2 + a - sh] * BLOCK + tid], m[a], const_cast<double*>(slots) + a * ostride);
+    }
+    const int mi = na > 0 ? nodes_of(e[2 + MAXA + na - 1]) : 1;
+    const double ti = na > 0 ? coord[e[2 + na - 1] * BLOCK + tid] : 0.0;
+    const double c = *cb;
+    if (mi == 3) contract_grid<NOUT, EXACT, 3>(m, slots, ostride, ti, val, n_out, c, acc);
+    else if (mi == 5) contract_grid<NOUT, EXACT, 5>(m, slots, ostride, ti, val, n_out, c, acc);
+    else if (mi == 9) contract_grid<NOUT, EXACT, 9>(m, slots, ostride, ti, val, n_out, c, acc);
+    else if (mi == 17) contract_grid<NOUT, EXACT, 17>(m, slots, ostride, ti, val, n_out, c, acc);
+    else contract_grid<NOUT, EXACT, 1>(m, slots, ostride, ti, val, n_out, c, acc);     // the constant grid (beta = 0)
+}
+
+// the latents of this workgroup's 256 points through LDS (the basis slots are free again), then every WAVE rebuilds the
+// dof values of its 64 points row by row: lane = field index, 512 contiguous bytes per store
+// twin of sparse_predict_kernel's `if (rc.field)` epilogue
+template <int NOUT>
+__device__ __forceinline__ void rebuild_field(const double (&acc)[NOUT], const Recon& rc, double* lds, long long i0, long long n, int tid) {
+    __syncthreads();                                 // (another wave may still read its basis slots)
+    double* lat = lds;                               // [BLOCK][rank]
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o)
+        if (o >= rc.lat0 && o < rc.lat0 + rc.rank) lat[tid * rc.rank + (o - rc.lat0)] = acc[o];
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int k0 = 0; k0 < rc.dof; k0 += 64) {
+        const int k = k0 + lane;
+        double bk[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) bk[q] = (k < rc.dof && q < rc.rank) ? rc.basis[(size_t)k * rc.rank + q] : 0.0;
+        for (int r = 0; r < 64; ++r) {
+            const long long p = i0 + wave * 64 + r;
+            if (p >= n) break;
+            const double* lr = lat + (wave * 64 + r) * rc.rank;
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (q < rc.rank) v = fma(lr[q], bk[q], v);
+            if (rc.norm == PEM_NORM_LOG10) v = exp10(v);
+            else if (rc.norm == PEM_NORM_LINEAR) v = v / rc.scale;
+            if (k < rc.dof) out_field_store(rc.field + (size_t)p * rc.dof + k, v);
+        }
+    }
+    __syncthreads();                                 // the next batch of points stages its bases over the latents
+}
+
+struct ChainStage {
+    const int32_t* index;
+    const double* coef;
+    const double* values;
+    int n_beta, n_out, max_outer, max_m;
+};
+
+// one stage's interpolant at this thread's point: the grids' dims[] are slots of the shared coordinate table `coord`
+template <int NOUT, bool EXACT>
+__device__ __forceinline__ void stage_predict(const ChainStage& s, const double* coord, double* basis, int tid, double (&acc)[NOUT]) {
+    const int n_out = EXACT ? NOUT : s.n_out;
+    const int ostride = s.max_m * BLOCK;
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) acc[o] = 0.0;
+    for (int bi = 0; bi < s.n_beta; ++bi)
+        grid_term<NOUT, EXACT>(s.index + (size_t)bi * IDX_STRIDE, s.values, n_out, s.coef + bi, coord, basis, tid, s.max_outer, ostride, acc);
+}
+
+// a coupling value y -> its normalised coordinate over [lo, lo + w]: the expression system.py's _predict_surrogate applies to the
+// inputs, left to right, no contraction (the torch composition of three single-table launches rounds the same way)
+__device__ __forceinline__ double coupling_coord(double y, double lo, double w) {
+#pragma clang fp contract(off)
+    return 2.0 * (y - lo) / w - 1.0;
+}
+
+// out rows: V_cc, I_B0, T, div_angle, T_c = T cos(div_angle) (plume.py:136-140), then plume outputs 1 .. n_out - 1 (the latents)
+template <int NOUT, bool EXACT>
+__global__ __launch_bounds__(BLOCK) void sparse_chain_kernel(long long n, int n_dim, int vcc_slot, int ib0_slot, ChainStage cat, ChainStage thr,
+                                                             ChainStage plu, double vcc_lo, double vcc_w, double ib0_lo, double ib0_w,
+                                                             const double* __restrict__ t, size_t ld, double* __restrict__ out,
+                                                             size_t ld_out, int basis_words, Recon rc) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* basis = lds;                                    // every stage's outer bases in turn; later: the latents [BLOCK][rank]
+    double* coord = lds + (size_t)basis_words * BLOCK;      // [n_dim][BLOCK]: the external coordinates and the two coupling slots
+    const int n_out = EXACT ? NOUT : plu.n_out;
+    const int tid = threadIdx.x;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long i0 = (long long)blockIdx.x * BLOCK; i0 < n; i0 += stride) {
+        const long long i = i0 + tid < n ? i0 + tid : n - 1;        // a dead lane recomputes the last point and stores nothing
+        for (int d = 0, r = 0; d < n_dim; ++d)
+            if (d != vcc_slot && d != ib0_slot) coord[d * BLOCK + tid] = t[(size_t)(r++) * ld + i];
+        // (each stage reads and writes this thread's own slots only: no barrier between the stages)
+        double vcc[1], thrust[2], plume[NOUT];
+        stage_predict<1, true>(cat, coord, basis, tid, vcc);
+        coord[vcc_slot * BLOCK + tid] = coupling_coord(vcc[0], vcc_lo, vcc_w);
+        stage_predict<2, true>(thr, coord, basis, tid, thrust);
+        coord[ib0_slot * BLOCK + tid] = coupling_coord(thrust[0], ib0_lo, ib0_w);
+        stage_predict<NOUT, EXACT>(plu, coord, basis, tid, plume);
+        if (i0 + tid < n) {
+            out[i] = vcc[0];
+            out[ld_out + i] = thrust[0];
+            out[2 * ld_out + i] = thrust[1];
+            out[3 * ld_out + i] = plume[0];
+            out[4 * ld_out + i] = thrust[1] * cos(plume[0]);
+#pragma unroll
+            for (int o = 1; o < NOUT; ++o)
+                if (EXACT || o < n_out) out[(size_t)(4 + o) * ld_out + i] = plume[o];
+        }
+        if (rc.field) rebuild_field<NOUT>(plume, rc, lds, i0, n, tid);
+    }
+}
+
+template <int NOUT, bool EXACT>
+void launch_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const ChainStage (&s)[3], const double (&map)[4], const double* t,
+                  size_t ld, double* out, size_t ld_out, int basis_words, const Recon& rc, hipStream_t st) {
+    size_t blocks = (n + BLOCK - 1) / BLOCK;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    const size_t lds = (size_t)(basis_words + n_dim) * BLOCK * sizeof(double);
+    if (lds > 64 * 1024) {
+        static pem::LdsAttrOnce attr;
+        (void)attr.ensure(reinterpret_cast<const void*>(sparse_chain_kernel<NOUT, EXACT>));      // a refusal shows as a launch error below
+    }
+    hipLaunchKernelGGL((sparse_chain_kernel<NOUT, EXACT>), dim3((unsigned)blocks), dim3(BLOCK), lds, st, (long long)n, n_dim, vcc_slot,
+                       ib0_slot, s[0], s[1], s[2], map[0], map[1], map[2], map[3], t, ld, out, ld_out, basis_words, rc);
+}
+
 }  // namespace
 
 namespace {
@@ -326,6 +477,61 @@ int sparse_predict(const char* who, size_t n, int n_dim, int n_beta, const int32
     return PEM_OK;
 }
 
+int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
+                         double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out, const Recon& rc,
+                         pem_stream_t stream) {
+    const char* who = "pem_sparse_predict_chain";
+    if (!stages) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL stage array", who);
+    if (n_dim < 2 || n_dim > PEM_SURR_MAX_DIM)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: 2 <= n_dim <= %d (the external coordinates and the two coupling slots)", who, PEM_SURR_MAX_DIM);
+    if (vcc_slot < 0 || vcc_slot >= n_dim || ib0_slot < 0 || ib0_slot >= n_dim || vcc_slot == ib0_slot)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the V_cc and I_B0 slots are two different coordinates < n_dim", who);
+    if (!std::isfinite(vcc_lo) || !std::isfinite(vcc_w) || !(vcc_w > 0.0) || !std::isfinite(ib0_lo) || !std::isfinite(ib0_w) || !(ib0_w > 0.0))
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: a coupling domain needs a finite lo and a finite width w > 0", who);
+    static const int need_out[3] = {1, 2, 0};          // cathode: V_cc; thruster: I_B0, T; plume: div_angle [, latents]
+    ChainStage cs[3];
+    int basis_words = 0;
+    for (int k = 0; k < 3; ++k) {
+        const pem_surr_stage& g = stages[k];
+        if (!g.index || !g.coef || !g.values) return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: NULL table", who, k);
+        if (g.n_beta < 1 || g.n_out < 1 || g.n_out > 16 || (need_out[k] && g.n_out != need_out[k]))
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: need n_beta >= 1 and n_out %s", who, k,
+                             k == 0 ? "== 1" : (k == 1 ? "== 2" : "in 1 .. 16"));
+        if (g.max_active < 0 || g.max_active > PEM_SURR_MAX_ACTIVE || g.max_level < 0 || g.max_level > PEM_SURR_MAX_LEVEL)
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: at most %d active dimensions of level <= %d per multi-index", who, k,
+                             PEM_SURR_MAX_ACTIVE, PEM_SURR_MAX_LEVEL);
+        cs[k] = ChainStage{g.index, g.coef, g.values, g.n_beta, g.n_out, g.max_active > 1 ? g.max_active - 1 : 0,
+                           g.max_level == 0 ? 1 : (1 << g.max_level) + 1};
+        if (cs[k].max_outer * cs[k].max_m > basis_words) basis_words = cs[k].max_outer * cs[k].max_m;
+    }
+    const int n_plume = stages[2].n_out;
+    if (rc.field && (rc.rank < 1 || rc.rank > 16 || rc.lat0 < 0 || rc.lat0 + rc.rank > n_plume || rc.dof < 1 || !rc.basis))
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the reconstructed field takes 1 <= rank <= 16 latent outputs lat0 .. lat0 + rank - 1 of the plume stage", who);
+    if (rc.field && rc.rank > basis_words) basis_words = rc.rank;
+    // the bases of one stage at a time: the largest stage's (max_active - 1) (2^max_level + 1), plus every coordinate
+    if ((size_t)(basis_words + n_dim) * BLOCK * sizeof(double) > 160 * 1024)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the largest stage's outer bases and %d coordinates do not fit the LDS", who, n_dim);
+    if (n == 0) return PEM_OK;
+    if ((n_dim > 2 && !t) || !out) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL array", who);
+    if ((n_dim > 2 && ld < n) || ld_out < n) return pem::fail(PEM_ERR_INVALID_ARG, "%s: leading dimension smaller than n", who);
+    if (int rc0 = pem::check_device()) return rc0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const double map[4] = {vcc_lo, vcc_w, ib0_lo, ib0_w};
+#define PEM_CHAIN(NOUT_, EXACT_) launch_chain<NOUT_, EXACT_>(n, n_dim, vcc_slot, ib0_slot, cs, map, t, ld, out, ld_out, basis_words, rc, st)
+    switch (n_plume) {
+        case 1: PEM_CHAIN(1, true); break;
+        case 2: PEM_CHAIN(2, true); break;
+        case 3: PEM_CHAIN(3, true); break;
+        case 4: PEM_CHAIN(4, true); break;
+        default:
+            if (n_plume <= 8) PEM_CHAIN(8, false);
+            else PEM_CHAIN(16, false);
+    }
+#undef PEM_CHAIN
+    HIP_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,6 +566,25 @@ int pem_sparse_predict_field_f64_dev(size_t n, int n_dim, int n_beta, const int3
     rc.scale = norm_scale;
     return sparse_predict("pem_sparse_predict_field", n, n_dim, n_beta, index, coef, values, n_out, t, ld, out, ld_out, 0, max_active, max_level,
                           rc, stream);
+}
+
+int pem_sparse_predict_chain_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                     double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out,
+                                     int lat0, int rank, int dof, int norm, double norm_scale, const double* basis, double* field,
+                                     pem_stream_t stream) {
+    Recon rc{};
+    if (field) {
+        if (norm != PEM_NORM_NONE && norm != PEM_NORM_LOG10 && norm != PEM_NORM_LINEAR)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_sparse_predict_chain: unknown norm %d", norm);
+        rc.basis = basis;
+        rc.field = field;
+        rc.dof = dof;
+        rc.rank = rank;
+        rc.lat0 = lat0;
+        rc.norm = norm;
+        rc.scale = norm_scale;
+    }
+    return sparse_predict_chain(n, n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w, ib0_lo, ib0_w, t, ld, out, ld_out, rc, stream);
 }
 
 }  // extern "C"

@@ -63,28 +63,37 @@ def nodes(level: int) -> np.ndarray:
 
 class SparseGridSurrogate:
     def __init__(self, varied, fixed: dict | None = None, priors=None, qoi=('V_cc', 'div_angle', 'T_c'), device=None,
-                 compression=None, num_compress: int = 500, compress_seed: int = 0, max_active: int = MAX_ACTIVE, max_level: int = MAX_LEVEL):
+                 compression=None, num_compress: int = 500, compress_seed: int = 0, max_active: int = MAX_ACTIVE, max_level: int = MAX_LEVEL,
+                 *, inputs=COUPLED_INPUTS, model=None, domains=None, n_coords=None):
         """qoi: scalar outputs (V_cc, div_angle, T_c) and at most one field ('j_ion').  compression: a fitted
         `compression.SVDCompression` of the field (as `process_compression` leaves it on the system's variable); None: one is
         fitted here on `num_compress` true-model evaluations at uniform random points of the varied inputs (gen_data.py:73-76
         default: 500) with log10 norm and reconstruction_tol 0.01 (yml:273-280).  max_active / max_level: what the refinement may
-        activate (<= MAX_ACTIVE, MAX_LEVEL)."""
+        activate (<= MAX_ACTIVE, MAX_LEVEL).
+
+        Keyword-only hooks for one COMPONENT of the graph (chain.py; the defaults are the coupled model): `inputs`, the component's
+        input names; `model(inputs, n)`, its true model (dict of physical numpy arrays -> [n][n_out] CUDA tensor of the scalars of
+        `qoi` in order, then the field's latents -- a field then needs its fitted `compression`); `domains`, {name: (lo, hi)} linear
+        domains of inputs without a prior (the coupling variables); `n_coords`, the coordinate count of the launch the tables
+        will run in (the LDS rule of `_admissible`)."""
         import torch
         self.priors = dict(sampling.PEM_V0_PRIORS if priors is None else priors)
         self.varied = tuple(varied)
         self.fixed = dict(fixed or {})
-        missing = [k for k in COUPLED_INPUTS if k not in self.varied and k not in self.fixed]
+        self.inputs, self.model, self.domains = tuple(inputs), model, dict(domains or {})
+        missing = [k for k in self.inputs if k not in self.varied and k not in self.fixed]
         if missing:
             raise ValueError(f'inputs neither varied nor fixed: {missing}')
         self.qoi = tuple(qoi)
         fields = [k for k in self.qoi if k in FIELDS]
-        if len(fields) > 1 or any(k not in FIELDS and k not in ('V_cc', 'div_angle', 'T_c') for k in self.qoi):
+        if len(fields) > 1 or (model is None and any(k not in FIELDS and k not in ('V_cc', 'div_angle', 'T_c') for k in self.qoi)):
             raise ValueError(f'qoi: scalars V_cc / div_angle / T_c and at most one field of {sorted(FIELDS)}; got {self.qoi}')
         if not (1 <= max_active <= MAX_ACTIVE and 0 <= max_level <= MAX_LEVEL):
             raise ValueError(f'max_active <= {MAX_ACTIVE}, max_level <= {MAX_LEVEL}')
         self.max_active, self.max_level = int(max_active), int(max_level)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.D = len(self.varied)
+        self.n_coords = self.D if n_coords is None else int(n_coords)
         self.index_set = []            # activated multi-indices (downward closed)
         self.candidates = []
         self.values = {}               # beta -> [prod(m)][n_out] numpy array of true-model outputs at the grid nodes
@@ -97,6 +106,8 @@ class SparseGridSurrogate:
         self.scalars = tuple(k for k in self.qoi if k not in FIELDS)
         self.compression = None
         if self.field:
+            if compression is None and model is not None:
+                raise ValueError('a component model interpolates a field through the compression it is handed')
             self.compression = compression if compression is not None else self._fit_compression(num_compress, compress_seed)
             if self.compression.basis is None or self.compression.basis.shape[0] != FIELDS[self.field]:
                 raise ValueError('the compression map is not one of the 91-point profile')
@@ -115,8 +126,12 @@ class SparseGridSurrogate:
         t = np.asarray(t, dtype=np.float64)
         out = {}
         for d, k in enumerate(self.varied):
-            p = self.priors[k]
             u = 0.5 * (t[d] + 1.0)
+            if k in self.domains:                       # a coupling variable: linear over its estimated domain
+                lo, hi = self.domains[k]
+                out[k] = lo + (hi - lo) * u
+                continue
+            p = self.priors[k]
             v = p.a + (p.b - p.a) * u
             out[k] = 10.0 ** v if p.kind == sampling.LOGUNIFORM else v
         return out
@@ -149,6 +164,8 @@ class SparseGridSurrogate:
     def _true_outputs(self, inputs: dict, n: int):
         """[n][n_out] CUDA tensor: the true model's scalars and -- fused, the profile is never stored -- the field's latents"""
         import torch
+        if self.model is not None:
+            return self.model(inputs, n)
         fused = self.field and self.compression.rank <= _lib.FUSED_LATENT_MAX_RANK
         batch = CoupledBatch(n, device=self.device, profile=bool(self.field) and not fused)
         batch.set_inputs(inputs)
@@ -211,10 +228,10 @@ class SparseGridSurrogate:
         if na > self.max_active or lv > self.max_level:
             return False
         # the predict kernel keeps the outer dimensions' bases of the WHOLE table's largest grid shape in LDS:
-        # ((most active dimensions - 1) x (2^highest level + 1) + D) doubles per thread of 256 within 160 KB
+        # ((most active dimensions - 1) x (2^highest level + 1) + coordinates) doubles per thread of 256 within 160 KB
         na_t = max([na] + [sum(1 for l in b if l > 0) for b in self.values])
         lv_t = max([lv] + [max(b) for b in self.values])
-        if (max(na_t - 1, 0) * ((1 << lv_t) + 1 if lv_t else 1) + self.D) * 256 * 8 > 160 * 1024:
+        if (max(na_t - 1, 0) * ((1 << lv_t) + 1 if lv_t else 1) + self.n_coords) * 256 * 8 > 160 * 1024:
             return False
         for d in range(self.D):            # downward closed: every backward neighbour is active
             if beta[d] > 0:
@@ -368,25 +385,7 @@ class SparseGridSurrogate:
             if not self.candidates:
                 break
             t = torch.rand((self.D, num_refine), dtype=torch.float64, device=self.device, generator=g) * 2 - 1
-            cands = list(self.candidates)
-            self._ensure_values(*cands)
-            # A prediction is linear in the combination coefficients: ONE launch gives every grid's interpolant at the
-            # points (active grids and candidates alike), and the current surrogate plus every trial index set is a row
-            # of a small matrix product -- instead of one table upload and one launch per candidate.
-            every = self.index_set + cands
-            col = {b: i for i, b in enumerate(every)}
-            cmat = np.zeros((1 + len(cands), len(every)))
-            for b, c in self.combination_coefficients(self.index_set).items():
-                cmat[0, col[b]] = c
-            for r, cand in enumerate(cands):
-                cmat[1 + r] = cmat[0]
-                for b, c in self.combination_delta(self.index_set, cand).items():
-                    cmat[1 + r, col[b]] += c
-            gv = self.grid_values(t, every)                                                     # [B][n_out][n]
-            f = (torch.from_numpy(cmat).to(self.device) @ gv.reshape(len(every), -1)).reshape(1 + len(cands), self.n_out, -1)
-            base = f[0]
-            scale = (base.max(dim=1).values - base.min(dim=1).values).clamp_min(1e-12)
-            errs = ((f[1:] - base).abs().mean(dim=2) / scale).max(dim=1).values.cpu().numpy()
+            cands, errs = self.candidate_indicators(t)
             k = int(np.argmax(errs))                                                            # first of equal maxima, as before
             best, best_err = cands[k], float(errs[k])
             self._activate(best)
@@ -394,3 +393,28 @@ class SparseGridSurrogate:
             if best_err < max_tol:
                 break
         return history
+
+    def candidate_indicators(self, t):
+        """(candidates, their error indicators) at the points t ([D][n] CUDA tensor): the max over the outputs of
+        mean |f_{I + beta} - f_I| / range(f_I).  Evaluates the true model at the candidates' nodes that have no values yet."""
+        import torch
+        cands = list(self.candidates)
+        self._ensure_values(*cands)
+        # A prediction is linear in the combination coefficients: ONE launch gives every grid's interpolant at the
+        # points (active grids and candidates alike), and the current surrogate plus every trial index set is a row
+        # of a small matrix product -- instead of one table upload and one launch per candidate.
+        every = self.index_set + cands
+        col = {b: i for i, b in enumerate(every)}
+        cmat = np.zeros((1 + len(cands), len(every)))
+        for b, c in self.combination_coefficients(self.index_set).items():
+            cmat[0, col[b]] = c
+        for r, cand in enumerate(cands):
+            cmat[1 + r] = cmat[0]
+            for b, c in self.combination_delta(self.index_set, cand).items():
+                cmat[1 + r, col[b]] += c
+        gv = self.grid_values(t, every)                                                     # [B][n_out][n]
+        f = (torch.from_numpy(cmat).to(self.device) @ gv.reshape(len(every), -1)).reshape(1 + len(cands), self.n_out, -1)
+        base = f[0]
+        scale = (base.max(dim=1).values - base.min(dim=1).values).clamp_min(1e-12)
+        errs = ((f[1:] - base).abs().mean(dim=2) / scale).max(dim=1).values.cpu().numpy()
+        return cands, errs

@@ -91,7 +91,8 @@ class Component:
     """What scripts/fit_surr.py:119-160 touches of an amisc component: `.name`, `.model_fidelity` (settable: the single-fidelity
     run of `train_surrogate` empties it), `.model_costs` ({alpha: cost of one evaluation at that fidelity}).  The three PEM-v0
     sub-models are evaluated by ONE coupled launch here, so they share one fidelity -- () -- and the cost unit is one coupled
-    evaluation split evenly; the reference's only multi-fidelity component is the Julia thruster (out of scope)."""
+    evaluation split evenly; the reference's only multi-fidelity component is the Julia thruster (out of scope).
+    fit(components=True) trains the components separately and sets their costs to their kernels' shares (chain.COST_SHARES)."""
 
     def __init__(self, name: str, share: float):
         self.name, self.model_fidelity, self.model_costs = name, (), {'()': float(share)}
@@ -209,14 +210,9 @@ class PemV0System:
     def _predict_surrogate(self, inputs):
         import torch
         s = self.surrogate
-        vals = [np.asarray(inputs[k].cpu() if hasattr(inputs[k], 'cpu') else inputs[k], dtype=np.float64) for k in s.varied]
-        shape = np.broadcast_shapes(*[v.shape for v in vals])
-        t = np.empty((s.D, int(np.prod(shape))))
-        for d, k in enumerate(s.varied):
-            p = s.priors[k]
-            v = np.broadcast_to(vals[d], shape).reshape(-1)
-            u = (np.log10(v) if p.kind == LOGUNIFORM else v)
-            t[d] = 2.0 * (u - p.a) / (p.b - p.a) - 1.0
+        if self._chained():
+            return self._predict_chain(inputs)
+        t, shape = self._external_coords(inputs, s.varied, s.priors)
         y = s.predict_fields(torch.from_numpy(t))
         out = {k: y[k].cpu().numpy().reshape(shape) for k in s.scalars}
         if s.field:                                          # the compressed field comes back reconstructed, with its coordinates
@@ -226,18 +222,101 @@ class PemV0System:
             out[f'{s.field}{COORDS_STR_ID}'] = _coords(shape, angle_grid())      # plume.py:153-157: every element the same alpha_rad array
         return out
 
+    def _chained(self):
+        from .chain import ChainedSurrogate
+        return isinstance(self.surrogate, ChainedSurrogate)
+
+    @staticmethod
+    def _external_coords(inputs, varied, priors):
+        """physical inputs -> ([len(varied)][n] normalised coordinates over the priors, loop shape): the input map of both
+        surrogates, and the expression the chained kernel applies to the coupling variables"""
+        vals = [np.asarray(inputs[k].cpu() if hasattr(inputs[k], 'cpu') else inputs[k], dtype=np.float64) for k in varied]
+        shape = np.broadcast_shapes(*[v.shape for v in vals]) if vals else np.shape(next(iter(inputs.values())))
+        t = np.empty((len(varied), int(np.prod(shape))))
+        for d, k in enumerate(varied):
+            p = priors[k]
+            v = np.broadcast_to(vals[d], shape).reshape(-1)
+            u = (np.log10(v) if p.kind == LOGUNIFORM else v)
+            t[d] = 2.0 * (u - p.a) / (p.b - p.a) - 1.0
+        return t, shape
+
+    def _predict_chain(self, inputs):
+        """the component surrogates chained through V_cc and I_B0, ONE pem_sparse_predict_chain_f64_dev launch"""
+        import torch
+        s = self.surrogate
+        t, shape = self._external_coords(inputs, s.varied, s.priors)
+        y = s.predict_fields(torch.from_numpy(t))
+        from .chain import CHAIN_OUTPUTS
+        out = {k: y[k].cpu().numpy().reshape(shape) for k in CHAIN_OUTPUTS}
+        if s.field:
+            f = y[s.field].cpu().numpy()
+            out[s.field] = f.reshape(shape + (f.shape[-1],))
+            from .models.plume import _coords, angle_grid
+            out[f'{s.field}{COORDS_STR_ID}'] = _coords(shape, angle_grid())
+        return out
+
+    def _test_error(self, qoi, test_set):
+        xt, yt = test_set
+        pred = self._predict_surrogate(xt)
+        # relative L2 error per target (fit_surr.py:121-133 plots exactly this); a log10-normalised field in its norm
+        nrm = lambda k, v: np.log10(np.asarray(v, dtype=np.float64)) if k == 'j_ion' else np.asarray(v, dtype=np.float64)   # noqa: E731
+        return {k: float(np.linalg.norm(nrm(k, pred[k]) - nrm(k, yt[k])) / np.linalg.norm(nrm(k, yt[k]))) for k in qoi if k in yt}
+
+    def _set_costs(self, shares):
+        for c, w in zip(self.components, shares):
+            c.model_costs = {'()': float(w)}
+
+    def _fit_components(self, qoi, varied, fixed, max_iter, max_tol, num_refine, seed, test_set):
+        """fit(components=True): one surrogate per component, cost-weighted greedy allocation (chain.py)"""
+        from .chain import COST_SHARES, ChainedSurrogate
+        field = 'j_ion' in qoi
+        s = self.surrogate
+        if not self._chained() or s.varied != tuple(k for k in COUPLED_INPUTS if k in set(varied)) or s.fixed != fixed \
+                or bool(s.field) != field:
+            comp = None
+            if field and self._outputs['j_ion'].compression is not None and self._outputs['j_ion'].compression.svd.basis is not None:
+                comp = self._outputs['j_ion'].compression.svd
+            self.surrogate = ChainedSurrogate(varied, fixed=fixed, priors=self.priors, field=field, compression=comp, seed=seed)
+            self.train_history = []
+        self._set_costs(COST_SHARES)
+        s = self.surrogate
+        for _it in range(max_iter):
+            step = s.refine_step(num_refine=num_refine, seed=seed + len(self.train_history))
+            if step is None:
+                break
+            c, beta, indicator, top = step
+            entry = {'added': beta, 'component': self.components[c].name, 'indicator': indicator,
+                     'component_evals': {cc.name: e for cc, e in zip(self.components, s.model_evals)},
+                     'model_evals': s.cost_weighted_evals()}
+            if test_set is not None:
+                entry['test_error'] = self._test_error(qoi, test_set)
+            self.train_history.append(entry)
+            if top < max_tol:
+                break
+        return self.train_history
+
     # ----------------------------------------------------------------------------------------------------- training
     def fit(self, targets=None, max_iter: int = 20, max_tol: float = 1e-3, num_refine: int = 1000, varied=None,
-            fixed: dict | None = None, seed: int = 0, test_set=None, **_):
+            fixed: dict | None = None, seed: int = 0, test_set=None, components: bool = False, **_):
         """Adaptive sparse-grid training over `varied` (default: every input not in `fixed`), keyword names of
         fit_surr.py:101-116.  Each iteration's (activated index, error indicator, model evaluations[, test error per
-        target]) is appended to `train_history`."""
+        target]) is appended to `train_history`.
+
+        components=True: one surrogate per component (cathode, thruster, plume) chained through V_cc and I_B0, as the reference
+        trains them (chain.py).  `targets` picks the test errors and whether the plume carries j_ion; each history entry also
+        names its `component` and the per-component cumulative `component_evals`, and `model_evals` is cost-weighted by the
+        components' `model_costs` (their kernels' bytes per evaluation, summing to 1)."""
         from .surrogate import SparseGridSurrogate
         fixed = dict(fixed or {})
         varied = tuple(varied) if varied is not None else tuple(k for k in COUPLED_INPUTS if k not in fixed)
         # targets=None: every output the surrogate can carry, as the reference trains all of a system's outputs -- the scalars and
         # j_ion through the latent coefficients of its SVD map (process_compression's, when it has run; else one fitted for the box)
         qoi = tuple(targets) if targets else ('V_cc', 'div_angle', 'T_c', 'j_ion')
+        if components:
+            return self._fit_components(qoi, varied, fixed, max_iter, max_tol, num_refine, seed, test_set)
+        if self._chained():                                 # back to one surrogate of the coupled graph
+            self.surrogate, self.train_history = None, []
+            self._set_costs([1.0 / len(self.components)] * len(self.components))
         if self.surrogate is None or self.surrogate.varied != varied or self.surrogate.qoi != qoi:
             comp = None
             if 'j_ion' in qoi and 'j_ion' in self._outputs and self._outputs['j_ion'].compression is not None \
@@ -251,12 +330,7 @@ class PemV0System:
             beta, indicator, evals = hist[0]
             entry = {'added': beta, 'indicator': indicator, 'model_evals': evals}
             if test_set is not None:
-                xt, yt = test_set
-                pred = self._predict_surrogate(xt)
-                # relative L2 error per target (fit_surr.py:121-133 plots exactly this); a log10-normalised field in its norm
-                nrm = lambda k, v: np.log10(np.asarray(v, dtype=np.float64)) if k == 'j_ion' else np.asarray(v, dtype=np.float64)   # noqa: E731
-                entry['test_error'] = {k: float(np.linalg.norm(nrm(k, pred[k]) - nrm(k, yt[k])) / np.linalg.norm(nrm(k, yt[k])))
-                                       for k in qoi if k in yt}
+                entry['test_error'] = self._test_error(qoi, test_set)
             self.train_history.append(entry)
             if indicator < max_tol:
                 break
@@ -264,7 +338,13 @@ class PemV0System:
 
     def get_allocation(self):
         """(cost_alloc, model_cost, overhead_cost, model_evals) as unpacked at fit_surr.py:119: one component-fidelity
-        pair here, cost in units of one coupled evaluation, no overhead bookkeeping."""
+        pair here, cost in units of one coupled evaluation, no overhead bookkeeping.  After fit(components=True): each component's
+        own evaluation count times its cost share, and the cost-weighted evaluations per iteration."""
+        if self._chained():
+            last = self.train_history[-1]['component_evals'] if self.train_history else {c.name: 0 for c in self.components}
+            cost_alloc = {c.name: {str(c.model_fidelity): float(last[c.name]) * c.model_costs['()']} for c in self.components}
+            evals = np.array([h['model_evals'] for h in self.train_history], dtype=np.float64)
+            return cost_alloc, {c.name: dict(c.model_costs) for c in self.components}, 0.0, np.diff(evals, prepend=0.0)
         evals = np.array([h['model_evals'] for h in self.train_history], dtype=np.float64)
         per_iter = np.diff(evals, prepend=0.0)
         total = float(evals[-1]) if evals.size else 0.0
@@ -280,7 +360,7 @@ class PemV0System:
         path = Path(save_dir if save_dir is not None else self.root_dir or '.') / filename
         state = {'name': self.name, 'drawn': self._drawn, 'seed': self.design.seed, 'train_history': self.train_history,
                  'compression': {v.name: v.compression.state() for v in self._outputs if v.compression is not None},
-                 'surrogate': None if self.surrogate is None else
+                 'surrogate': None if self.surrogate is None or self._chained() else
                  {'varied': self.surrogate.varied, 'fixed': self.surrogate.fixed, 'qoi': self.surrogate.qoi,
                   'index_set': self.surrogate.index_set, 'candidates': self.surrogate.candidates,
                   'values': self.surrogate.values, 'model_evals': self.surrogate.model_evals,
@@ -288,6 +368,8 @@ class PemV0System:
                   'compression': None if self.surrogate.compression is None else
                   {'rank': self.surrogate.compression.rank, 'basis': self.surrogate.compression.basis.cpu().numpy(),
                    'relative_error': getattr(self.surrogate.compression, 'relative_error', None)}}}
+        if self._chained():
+            state['chain'] = self.surrogate.state()
         with open(path, 'wb') as fd:
             pickle.dump(state, fd)
         return path
@@ -316,6 +398,10 @@ class PemV0System:
             s.index_set, s.candidates, s.values, s.model_evals = st['index_set'], st['candidates'], st['values'], st['model_evals']
             s.rebuild_device_tables()
             self.surrogate = s
+        if state.get('chain') is not None:                   # fit(components=True); files without the key load as before
+            from .chain import COST_SHARES, ChainedSurrogate
+            self.surrogate = ChainedSurrogate.from_state(state['chain'], priors=self.priors)
+            self._set_costs(COST_SHARES)
         return self
 
 

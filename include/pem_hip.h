@@ -325,6 +325,29 @@ int pem_sparse_predict_field_f64_dev(size_t n, int n_dim, int n_beta, const int3
                                      int n_out, const double* t, size_t ld, double* out, size_t ld_out, int max_active, int max_level,
                                      int lat0, int rank, int dof, int norm, double norm_scale, const double* basis, double* field,
                                      pem_stream_t stream);
+/* The component chain in one launch (round 5): one surrogate per component, chained through the coupling variables as the reference
+ * trains them (scripts/pem_v0/pem_v0_SPT-100.yml:4-6,62-63,215-219: Cathode V_cc -> Thruster; Thruster I_B0 -> Plume).  stages: HOST
+ * array of three tables in the format above (device arrays), cathode, thruster, plume; their dims[] are slots of ONE coordinate table of
+ * n_dim slots.  t: [n_dim - 2][ld], the external coordinates of every slot but vcc_slot and ib0_slot, in slot order.  Per point:
+ *   V_cc       = cathode(t)                          (n_out == 1)
+ *   slot vcc   = 2.0 * (V_cc - vcc_lo) / vcc_w - 1.0  (left to right, no contraction: system.py's input map)
+ *   I_B0, T    = thruster(t)                         (n_out == 2)
+ *   slot ib0   = 2.0 * (I_B0 - ib0_lo) / ib0_w - 1.0
+ *   div_angle, p_1 .. p_{n_out-1} = plume(t)         (1 <= n_out <= 16)
+ *   T_c        = T * cos(div_angle)                  (plume.py:136-140)
+ * out: [4 + n_out(plume)][ld_out] rows V_cc, I_B0, T, div_angle, T_c, p_1, ...  field: NULL, or as pem_sparse_predict_field_f64_dev over
+ * the plume stage's outputs lat0 .. lat0 + rank - 1.  LDS: the largest stage's bases plus n_dim coordinates, the 160 KB rule above.
+ * Every argument is checked before the device is, so a malformed call fails with PEM_ERR_INVALID_ARG without a GPU too. */
+typedef struct pem_surr_stage {
+    const int32_t* index;
+    const double* coef;
+    const double* values;
+    int n_beta, n_out, max_active, max_level;
+} pem_surr_stage;
+int pem_sparse_predict_chain_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                     double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out,
+                                     int lat0, int rank, int dof, int norm, double norm_scale, const double* basis, double* field,
+                                     pem_stream_t stream);
 
 /* ---- per-column order statistics over the sample axis -------------------------------------------------------------
  * The percentiles of scripts/gen_data.py:125-174 (`np.percentile(arr, 25 | 75, axis=0)`, NaN / interquartile-range masks) and
