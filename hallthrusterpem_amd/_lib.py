@@ -49,6 +49,11 @@ SIGNATURES = {
     'pem_coupled_loglik_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int] + [_dp] * 4 + [_dp] * 5 + [_dp]),
     'pem_coupled_system_loglik_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int]
                                           + [_dp] * 5 + [_dp]),
+    'pem_coupled_system_predict_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int]
+                                           + [_dp] * 4 + [_sz, _dp, _dp]),
+    'pem_predictive_inputs_f64_dev': (C.c_int, [_sz, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, _dp, _dp, _sz, C.c_int,
+                                                _dp, C.c_uint32, _dp, _sz, _dp]),
+    'pem_predictive_noise_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _sz, _dp]),
     'pem_coupled_latent_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp] + [_dp] * 4 + [_dp]),
     'pem_loglik_marginal_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, _f8, _f8, _dp, _dp, _dp]),
     'pem_log_prior_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),

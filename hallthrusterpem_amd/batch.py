@@ -196,6 +196,31 @@ class CoupledBatch:
         _lib.check(rc)
         return out
 
+    def run_system_predict(self, likelihood, pred, qoi: bool = False, stream=None):
+        """Coupled evaluation + the model value at every record of a `likelihood.SystemLikelihood` in one launch
+        (`pem_coupled_system_predict_f64_dev`): sample i = d n_cond + c writes the records of condition c to pred[d, record].
+        pred: a (ceil(n / n_cond), >= n_rec) float64 tensor with unit column stride; its padding records are not written.
+        qoi: also write V_cc / div_angle / T_c / invalid as `run` does."""
+        import torch
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        if self.layout != 'soa':
+            raise NotImplementedError("the fused prediction launch reads SoA inputs: use layout='soa'")
+        lk = likelihood
+        if lk.sweep_radius != self.radius:
+            raise ValueError(f'the likelihood\'s j_ion data are at r = {lk.sweep_radius}, the batch sweeps r = {self.radius}')
+        rows = -(-self.n // lk.n_cond)
+        if (pred.dtype != torch.float64 or pred.dim() != 2 or pred.device != self.device or pred.stride(1) != 1
+                or pred.shape[0] < rows or pred.shape[1] < lk.n_rec):
+            raise ValueError(f'pred must be a float64 ({rows}, >= {lk.n_rec}) tensor on {self.device} with unit column stride')
+        p = lambda t: C.c_void_p(t.data_ptr())                                   # noqa: E731
+        z0, z1, ncells = lk.uion_grid
+        rc = _lib.load().pem_coupled_system_predict_f64_dev(
+            self.n, constants.TORR_2_PA, self.radius, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
+            p(lk.node), z0, z1, ncells, *([p(self.qoi[0]), p(self.qoi[1]), p(self.qoi[2])] if qoi else [None] * 3), p(pred),
+            pred.stride(0), p(self.invalid) if qoi else None, C.c_void_p(s.cuda_stream))
+        _lib.check(rc)
+        return pred
+
     def run_latent(self, compression, out=None, stream=None):
         """Coupled evaluation + `compression.SVDCompression.compress(j_ion)` in one launch
         (`pem_coupled_latent_f64_dev`): the latents are accumulated in the registers of the angle loop, the profile is

@@ -120,6 +120,13 @@ struct SystemTable {
     int ncells;
 };
 
+// record predictions (JMODE 7): JMODE 6's table, and where the model value of every record goes -- pred[d * ld_pred + r]
+// for record r of sample i = d * n_cond + c (pem_coupled_system_predict_f64_dev)
+struct SystemPredict : SystemTable {
+    double* pred;
+    long long ld_pred;
+};
+
 // the per-sample inputs of one lane, prefetched one tile ahead
 template <bool COUPLED>
 struct SampleIn {
@@ -229,6 +236,8 @@ __device__ __forceinline__ SampleIn<true> generate_sample(const McDesign& mc, co
 //            5: the same without the stores -- the percentiles of a profile that is never written
 //            6: fused multi-QoI likelihood -- JMODE 3's j_ion records against the staged profile, plus V_cc, thrust and u_ion
 //               records of the sample's condition in the epilogue (system_epilogue_sum)
+//            7: record predictions -- JMODE 6's table, the model value of every record stored instead of compared
+//               (j_ion in the rounds, jion_records_store; the others in the epilogue, system_epilogue_store)
 // LDS map (doubles): shared by the workgroup: simpson[96][2] | dpoly[32*12];  per wave: params[NROWS][64] |
 // tile[S*91] | 2 (sink).  The Simpson table is padded with zero weights to L*CH <= 96 entries so the angle loop
 // needs no branch.  The den/num partial sums of a round reuse the rows of `params` that the round has consumed.
@@ -243,7 +252,7 @@ constexpr int QPOLY_DOUBLES = (PEM_NDI + PEM_NQB) * PEM_NDC * 2;
 template <int L, int JMODE>
 constexpr int wave_lds_doubles() {
     return param_rows<L>() * WAVE +
-           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5 || JMODE == 6) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
+           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5 || JMODE == 6 || JMODE == 7) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
 }
 template <int L, int JMODE>
 constexpr int fast_lds_doubles() { return TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>(); }
@@ -282,6 +291,8 @@ struct WaveLds {
     const int2* span;        // JMODE 6: [n_cond][4] {first record, count} of each kind (meas holds the records)
     const double* unode;     // JMODE 6: [max(n_node, 2)] u_ion denominators 1 + exp(-100 (z_k - 0.04))
     int n_unode;
+    double* pred;            // JMODE 7: the [draws][ld_pred] predictions in HBM
+    long long ld_pred;
     const double2* simpson;  // [96] {cden, cnum}
     const double* poly;      // [32*12]
     const double2* qpoly;    // reduced-QoI mode: [(32+64)*12] {Qd, Qn} coefficients of the Simpson functionals, or nullptr
@@ -554,6 +565,32 @@ __device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec,
     return acc;
 }
 
+// JMODE 7: lane c's share of the j_ion records of one sample, the model values JMODE 6 compares, stored to out[record]
+template <int L, typename JT>
+__device__ __forceinline__ void jion_records_store(const double4* mt, int n_rec, const JT* row, int c, double* out) {
+    constexpr int MU = PEM_LOGLIK_MU;
+    for (int a0 = c; a0 < n_rec; a0 += MU * L) {
+        double4 e[MU];
+        double lo_v[MU], hi_v[MU];
+#pragma unroll
+        for (int u = 0; u < MU; ++u) e[u] = mt[a0 + u * L < n_rec ? a0 + u * L : a0];
+#pragma unroll
+        for (int u = 0; u < MU; ++u) {
+            const int k = __double_as_longlong(e[u].w) & 0x7f;
+            lo_v[u] = row[k];
+            hi_v[u] = row[k + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < MU; ++u)
+            if (a0 + u * L < n_rec) out[a0 + u * L] = fma(e[u].x, hi_v[u] - lo_v[u], lo_v[u]);
+    }
+}
+
+// JMODE 7: the first record of sample t * 64 + j in pred, u = (t * 64) % n_cond + j: row (t * 64 + j) / n_cond
+__device__ __forceinline__ double* pred_row(const WaveLds& m, long long t, unsigned u, int n_cond) {
+    return m.pred + ((t * WAVE) / n_cond + (long long)(u / (unsigned)n_cond)) * m.ld_pred;
+}
+
 // u_ion grid node c of sim_hallthruster.jl:46-47, z = range(z0, z1, length = ncells), and the denominator of u_ion there:
 // one expression for thruster_uion_kernel and the fused multi-QoI mode, so that both see the same node values
 __device__ __forceinline__ double uion_z(double z0, double z1, int ncells, int c) {
@@ -585,6 +622,23 @@ __device__ __forceinline__ double system_epilogue_sum(double ll, const WaveLds& 
         ll = fma(-0.5 * z, z, ll);
     }
     return ll;
+}
+
+// JMODE 7 epilogue, one lane per sample: the model values system_epilogue_sum compares, stored to out[record]
+__device__ __forceinline__ void system_epilogue_store(const WaveLds& m, unsigned cond, double V_cc, double thrust, double v_exh,
+                                                      double* out) {
+    const double4* rec = reinterpret_cast<const double4*>(m.meas);
+    const int2* sp = m.span + 4 * cond;
+    const int2 rv = sp[PEM_SYS_VCC], rt = sp[PEM_SYS_T], ru = sp[PEM_SYS_UION];
+    for (int i = rv.x; i < rv.x + rv.y; ++i) out[i] = V_cc;
+    for (int i = rt.x; i < rt.x + rt.y; ++i) out[i] = thrust;
+    const unsigned pmax = (unsigned)(m.n_unode < 2 ? 0 : m.n_unode - 2);
+    for (int i = ru.x; i < ru.x + ru.y; ++i) {
+        const double4 e = rec[i];
+        const unsigned p = min((unsigned)__double_as_longlong(e.w), pmax);
+        const double u0 = v_exh / m.unode[p], u1 = v_exh / m.unode[p + 1];
+        out[i] = fma(e.x, u1 - u0, u0);
+    }
 }
 
 // One 64-sample tile.  FULL = every sample of the tile exists (the steady state of the persistent loop:
@@ -773,12 +827,22 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
                 }
                 wave_lds_sync();
                 const long long first = t * WAVE + (long long)round * S;
-                if constexpr (JMODE == 3 || JMODE == 6) {
+                if constexpr (JMODE == 3 || JMODE == 6 || JMODE == 7) {
                     static_assert(2 * L < param_rows<L>(), "row 2L of `params` carries the likelihood sum");
                     // measured current densities against the staged profile: lane (s, c) takes measurements c, c+L, ...
                     // of its sample's condition (sample index mod n_cond); the sample's sum goes to row 2L of `params`
                     const unsigned cond = ((unsigned)((t * WAVE) % io.n_cond) + (unsigned)(round * S + s)) % (unsigned)io.n_cond;
                     const JT* row = tile + s * NANG;
+                    if constexpr (JMODE == 7) {   // the values themselves, to the sample's row of pred
+                        const int2 sp = m.span[4 * cond + PEM_SYS_JION];
+                        if (FULL || first + s < io.n) {
+                            const unsigned u = (unsigned)((t * WAVE) % io.n_cond) + (unsigned)(round * S + s);
+                            jion_records_store<L>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c,
+                                                  pred_row(m, t, u, io.n_cond) + sp.x);
+                        }
+                        wave_lds_sync();
+                        continue;
+                    }
                     double acc;
                     if constexpr (JMODE == 3) {
                         const double4* mt = reinterpret_cast<const double4*>(m.meas) + cond * (io.n_ang | 1);   // {weight, y, 1/std, k}
@@ -864,12 +928,19 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
             io.loglik[g] = system_epilogue_sum(params[(2 * L) * WAVE + lane], m, cond, V_cc, thrust, v_exh);
         }
     }
+    if constexpr (JMODE == 7) {
+        if (live) {
+            const unsigned u = (unsigned)((t * WAVE) % io.n_cond) + (unsigned)lane;
+            system_epilogue_store(m, u % (unsigned)io.n_cond, V_cc, thrust, v_exh, pred_row(m, t, u, io.n_cond));
+        }
+    }
     if (live) {
-        stream_store1(acos(cos_div), io.div + g);
-        if (have_T) stream_store1(thrust * cos_div, io.Tc + g);
+        // (the record predictions take V_cc, div_angle and T_c as optional outputs)
+        if (JMODE != 7 || io.div) stream_store1(acos(cos_div), io.div + g);
+        if (have_T && (JMODE != 7 || io.Tc)) stream_store1(thrust * cos_div, io.Tc + g);
         if (io.invalid) io.invalid[g] = (uint8_t)((inv_mask >> lane) & 1);
         if constexpr (COUPLED) {
-            stream_store1(V_cc, cio.V_cc + g);
+            if (JMODE != 7 || cio.V_cc) stream_store1(V_cc, cio.V_cc + g);
             if (cio.I_B0) stream_store1(I_B0, cio.I_B0 + g);
             if (cio.T) stream_store1(thrust, cio.T + g);
         }
@@ -888,7 +959,9 @@ constexpr int min_waves_per_simd() { return (MC && JMODE == 0) ? 3 : 1; }
 // likelihood mode its measurement table.
 struct NoDesign {};
 template <bool MC, int JMODE = 0>
-using DesignArg = typename std::conditional<MC, McDesign, typename std::conditional<JMODE == 6, SystemTable, NoDesign>::type>::type;
+using DesignArg = typename std::conditional<
+    MC, McDesign,
+    typename std::conditional<JMODE == 6, SystemTable, typename std::conditional<JMODE == 7, SystemPredict, NoDesign>::type>::type>::type;
 
 // bytes of LDS the counting modes add per workgroup: brackets' {loh, words} [91][NQ] | below counters [NQ][91] | premask thresholds [91] x 16
 template <int NQ, bool PM>
@@ -945,7 +1018,9 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, 
     m.span = nullptr;
     m.unode = nullptr;
     m.n_unode = 0;
-    if constexpr (JMODE == 6) {   // records | spans | u_ion denominators behind the per-wave regions (layout: system_lds_bytes)
+    m.pred = nullptr;
+    m.ld_pred = 0;
+    if constexpr (JMODE == 6 || JMODE == 7) {   // records | spans | u_ion denominators behind the per-wave regions (system_lds_bytes)
         double* meas = lds + TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>();
         for (int i = tid; i < 4 * mc.n_rec; i += WAVE * WPB) meas[i] = mc.rec[i];
         int2* span = reinterpret_cast<int2*>(meas + 4 * mc.n_rec);
@@ -961,6 +1036,10 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, 
         m.span = span;
         m.unode = unode;
         m.n_unode = mc.n_node;
+        if constexpr (JMODE == 7) {
+            m.pred = mc.pred;
+            m.ld_pred = mc.ld_pred;
+        }
     }
 
     using QC = typename std::conditional<(NQ > 0), QCount, NoCount>::type;
@@ -2005,9 +2084,10 @@ int r1_per_cu(size_t lds, long long* per_cu) {
 // `grid_only`: report the grid the launch would use (the counting modes size their record buffer by it) and launch nothing
 template <int L, bool COUPLED, int JMODE, bool MC = false, int NQ = 0, bool PM = false>
 int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McDesign& mc = McDesign{}, unsigned* grid_only = nullptr,
-              const SystemTable* sys = nullptr) {
+              const SystemTable* sys = nullptr, const SystemPredict* pr = nullptr) {
     size_t lds = r1_lds_bytes<L, JMODE, MC, NQ, PM>(io);
     if constexpr (JMODE == 6) lds += system_lds_bytes(io.n_cond, *sys);
+    if constexpr (JMODE == 7) lds += system_lds_bytes(io.n_cond, *pr);
     const long long ntiles = (io.n + WAVE - 1) / WAVE;
     unsigned grid = 0;
     auto kern = plume_r1_kernel<L, COUPLED, JMODE, MC, NQ, PM>;
@@ -2025,6 +2105,7 @@ int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McD
     }
     if constexpr (MC) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, mc);
     else if constexpr (JMODE == 6) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *sys);
+    else if constexpr (JMODE == 7) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *pr);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, NoDesign{});
     HIP_TRY(hipGetLastError());
     return PEM_OK;
@@ -2861,6 +2942,36 @@ int pem_coupled_system_loglik_f64_dev(size_t n, double torr2pa, double radius, c
     CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
     const SystemTable tab{rec, span, node, n_rec, n_node, z0, z1, ncells};
     return launch_r1<4, true, 6>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, &tab);
+}
+
+// ---- coupled + the model value at every record of the multi-QoI table (JMODE 6's table, stored instead of compared) --------
+int pem_coupled_system_predict_f64_dev(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a,
+                                       const double* T_e, const double* V_vac, const double* Pstar, const double* P_T,
+                                       const double* mdot_a, const double* a_1, const double* c0, const double* c1, const double* c2,
+                                       const double* c3, const double* c4, const double* c5, const double* sigma_cex, int n_cond,
+                                       int n_rec, const double* rec, const int32_t* span, int n_node, const int32_t* node, double z0,
+                                       double z1, int ncells, double* V_cc, double* div_angle, double* T_c, double* pred,
+                                       size_t ld_pred, uint8_t* invalid, pem_stream_t stream) {
+    if (n_cond < 1 || n_cond > PEM_FUSED_SYSTEM_MAX_RECORDS || n_rec < 0 || n_rec > PEM_FUSED_SYSTEM_MAX_RECORDS || n_node < 0 ||
+        n_node > 2 * PEM_FUSED_SYSTEM_MAX_RECORDS)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict: 1 <= n_cond <= %d, 0 <= n_rec <= %d, 0 <= n_node <= %d "
+                    "(PEM_FUSED_SYSTEM_MAX_RECORDS)", PEM_FUSED_SYSTEM_MAX_RECORDS, PEM_FUSED_SYSTEM_MAX_RECORDS,
+                    2 * PEM_FUSED_SYSTEM_MAX_RECORDS);
+    if (n_node > 0 && ncells < 2) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict: need at least 2 u_ion grid points");
+    if (ld_pred < (size_t)n_rec) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict: ld_pred < n_rec");
+    if (n == 0) return PEM_OK;
+    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !mdot_a || !a_1 || !c0 || !c1 || !c2 || !c3 || !c4 || !c5 ||
+        !sigma_cex || (n_rec > 0 && !rec) || !span || (n_node > 0 && !node) || !pred)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict: NULL array");
+    if (int rc = check_device()) return rc;
+    PlumeIO io{(long long)n, torr2pa, radius, P_b, c0, c1, c2, c3, c4, c5, sigma_cex, nullptr, nullptr, nullptr, div_angle, T_c, invalid, nullptr,
+               nullptr, nullptr, nullptr, nullptr, nullptr, n_cond, 0};
+    CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
+    SystemPredict pr;
+    static_cast<SystemTable&>(pr) = SystemTable{rec, span, node, n_rec, n_node, z0, z1, ncells};
+    pr.pred = pred;
+    pr.ld_pred = (long long)ld_pred;
+    return launch_r1<4, true, 7>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, nullptr, &pr);
 }
 
 // ---- coupled, mixed precision: fp64 arithmetic, the 91-point profile stored as fp32 -----------------

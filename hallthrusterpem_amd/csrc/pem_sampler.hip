@@ -206,3 +206,125 @@ extern "C" int pem_sobol_partial_f64_dev(size_t m, int nq, size_t ld, const doub
     HIP_TRY(hipGetLastError());
     return PEM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Predictive checks (hallthrusterpem_amd/predictive.py; scripts/pem_v0/monte_carlo.py:42-60,63-300): the inputs of
+// n_draws x n_cond samples -- the design's draws, each condition's operating row, theta drawn from a posterior table or
+// kept from the prior -- and a Gaussian-noise copy of the predictions, both counter-based (oracle/sampler_np.py restates them).
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int PRED_DIM = 15;     // the coupled inputs, in COUPLED_INPUTS order
+constexpr int PRED_OP_ROWS[3] = {0, 1, 6};   // P_b, V_a, mdot_a: columns 0, 1, 2 of an operating row
+
+struct PredTable {
+    int32_t kind[PRED_DIM];
+    double a[PRED_DIM], b[PRED_DIM];
+    int32_t role[PRED_DIM];      // -1: the design's draw;  0..2: operating column;  3 + j: column j of the theta table
+};
+
+__global__ __launch_bounds__(256) void predictive_inputs_kernel(long long n, int n_cond, uint64_t first, uint64_t seed,
+                                                                uint32_t stream, PredTable tab, const double* __restrict__ op,
+                                                                const double* __restrict__ samples, uint64_t n_samples,
+                                                                int n_theta, uint32_t theta_stream, double* __restrict__ out,
+                                                                size_t ld) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t g = first + (uint64_t)i;
+        const int c = (int)(i % n_cond);
+        uint64_t idx = 0;   // PEM_PREDICTIVE_THETA_INDEX: the multiply-high of the first Philox word by S
+        if (samples) idx = ((uint64_t)philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), 0u, theta_stream, k0, k1).x * n_samples) >> 32;
+        for (int d0 = 0; d0 < PRED_DIM; d0 += 2) {
+            const bool draw0 = tab.role[d0] < 0 || (tab.role[d0] >= 3 && !samples);
+            const bool draw1 = d0 + 1 < PRED_DIM && (tab.role[d0 + 1] < 0 || (tab.role[d0 + 1] >= 3 && !samples));
+            Philox4 r{0, 0, 0, 0};
+            if (draw0 || draw1) r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)(d0 >> 1), stream, k0, k1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int d = d0 + h;
+                if (d >= PRED_DIM) break;
+                const int role = tab.role[d];
+                double v;
+                if (h == 0 ? draw0 : draw1) v = transform_call(tab.kind[d], tab.a[d], tab.b[d], h == 0 ? u53(r.x, r.y) : u53(r.z, r.w));
+                else if (role < 3) v = op[3 * c + role];
+                else v = samples[idx * (uint64_t)n_theta + (uint64_t)(role - 3)];
+                out[(size_t)d * ld + (size_t)i] = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void predictive_noise_kernel(long long n_rows, int m, const double* __restrict__ pred,
+                                                               size_t ld_pred, const double* __restrict__ sigma, uint64_t first,
+                                                               uint64_t seed, uint32_t stream, double* __restrict__ out,
+                                                               size_t ld_out) {
+    const long long total = n_rows * (long long)m;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const long long s = i / m;
+        const int j = (int)(i - s * m);
+        const uint64_t g = first + (uint64_t)s;
+        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)j, stream, k0, k1);
+        out[(size_t)s * ld_out + j] = pred[(size_t)s * ld_pred + j] + transform_call(PEM_DIST_NORMAL, 0.0, sigma[j], u53(r.x, r.y));
+    }
+}
+
+unsigned grid_for(long long total) {
+    long long blocks = (total + 255) / 256;
+    return (unsigned)(blocks > 256 * 16 ? 256 * 16 : blocks);
+}
+
+}  // namespace
+
+extern "C" int pem_predictive_inputs_f64_dev(size_t n, int n_cond, uint64_t first_index, uint64_t seed, uint32_t stream_id,
+                                             const int32_t* kind, const double* a, const double* b, const double* operating,
+                                             const double* samples, size_t n_samples, int n_theta, const int32_t* theta_rows,
+                                             uint32_t theta_stream, double* out, size_t ld, pem_stream_t stream) {
+    if (n_cond < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: n_cond must be >= 1");
+    if (n_theta < 0 || n_theta > PRED_DIM || (n_theta > 0 && !theta_rows))
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: 0 <= n_theta <= %d with its rows", PRED_DIM);
+    if (samples && (n_samples < 1 || n_samples > 0xFFFFFFFFull || n_theta < 1))
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: a theta table needs 1 <= S < 2^32 rows and n_theta >= 1");
+    if (!kind || !a || !b || !operating || !out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: NULL array");
+    if (ld < n) return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: leading dimension smaller than n");
+    PredTable tab;
+    for (int d = 0; d < PRED_DIM; ++d) {
+        if (kind[d] < 0 || kind[d] > PEM_DIST_NORMAL)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: unknown distribution kind %d for dimension %d", kind[d], d);
+        tab.kind[d] = kind[d];
+        tab.a[d] = a[d];
+        tab.b[d] = b[d];
+        tab.role[d] = -1;
+    }
+    for (int k = 0; k < 3; ++k) tab.role[PRED_OP_ROWS[k]] = k;
+    for (int j = 0; j < n_theta; ++j) {
+        const int d = theta_rows[j];
+        if (d < 0 || d >= PRED_DIM || tab.role[d] != -1)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_inputs: theta row %d is not a free input (or repeated)", d);
+        tab.role[d] = 3 + j;
+    }
+    if (n == 0) return PEM_OK;
+    if (int rc = pem::check_device()) return rc;
+    hipLaunchKernelGGL(predictive_inputs_kernel, dim3(grid_for((long long)n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       (long long)n, n_cond, first_index, seed, stream_id, tab, operating, samples, (uint64_t)n_samples, n_theta,
+                       theta_stream, out, ld);
+    HIP_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
+extern "C" int pem_predictive_noise_f64_dev(size_t n_rows, int m, const double* pred, size_t ld_pred, const double* sigma,
+                                            uint64_t first_row, uint64_t seed, uint32_t stream_id, double* out, size_t ld_out,
+                                            pem_stream_t stream) {
+    if (m < 0 || ld_pred < (size_t)m || ld_out < (size_t)m)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_noise: m >= 0 and leading dimensions >= m");
+    if (n_rows == 0 || m == 0) return PEM_OK;
+    if (!pred || !sigma || !out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_predictive_noise: NULL array");
+    if (int rc = pem::check_device()) return rc;
+    hipLaunchKernelGGL(predictive_noise_kernel, dim3(grid_for((long long)n_rows * m)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), (long long)n_rows, m, pred, ld_pred, sigma, first_row, seed, stream_id,
+                       out, ld_out);
+    HIP_TRY(hipGetLastError());
+    return PEM_OK;
+}

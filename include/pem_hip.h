@@ -190,6 +190,24 @@ int pem_sample_tiled_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint
                              const int32_t* kind, const double* a, const double* b, int swap_dim, double* out,
                              pem_stream_t stream);
 
+/* Predictive checks (scripts/pem_v0/monte_carlo.py:42-60,63-300; hallthrusterpem_amd/predictive.py).
+ * pem_predictive_inputs_f64_dev fills the [15][ld] SoA inputs (COUPLED_INPUTS order) of n samples, sample i belonging to
+ * condition c = i mod n_cond: every input starts as draw first_index + i of the design (pem_sample_f64_dev's numbers for
+ * seed, stream_id, kind/a/b: HOST arrays of 15), then rows P_b, V_a, mdot_a become operating[c][0..2] (DEVICE [n_cond][3]) and,
+ * when samples (DEVICE [n_samples][n_theta]) is not NULL, row theta_rows[j] (HOST [n_theta]) becomes samples[idx_i][j] with
+ *   idx_i = (x * n_samples) >> 32,   x = word 0 of Philox4x32-10(counter = (g_lo, g_hi, 0, theta_stream), key = seed), g = first_index + i
+ * (PEM_PREDICTIVE_THETA_INDEX; 1 <= n_samples < 2^32): theta drawn with replacement, independently for every sample.  With
+ * samples NULL the theta rows keep the prior draw (the prior predictive).
+ * pem_predictive_noise_f64_dev: out[s][j] = pred[s][j] + sigma[j] Phi^-1(u53(w0, w1)), (w0, w1) words 0, 1 of
+ * Philox4x32-10(counter = (g_lo, g_hi, j, stream_id), key = seed), g = first_row + s; pred, out [n_rows][ld], sigma DEVICE [m]. */
+int pem_predictive_inputs_f64_dev(size_t n, int n_cond, uint64_t first_index, uint64_t seed, uint32_t stream_id,
+                                  const int32_t* kind, const double* a, const double* b, const double* operating,
+                                  const double* samples, size_t n_samples, int n_theta, const int32_t* theta_rows,
+                                  uint32_t theta_stream, double* out, size_t ld, pem_stream_t stream);
+int pem_predictive_noise_f64_dev(size_t n_rows, int m, const double* pred, size_t ld_pred, const double* sigma,
+                                 uint64_t first_row, uint64_t seed, uint32_t stream_id, double* out, size_t ld_out,
+                                 pem_stream_t stream);
+
 /* Saltelli accumulation for the Sobol' estimators (uq.sobol_sa at scripts/pem_v0/sobol.py:113 -- uqtils, third-party,
  * parity UNPINNED; estimators stated in hallthrusterpem_amd/drivers.py).  fA / fB / fAB: [nq][ld] QoI rows of the
  * A, B and AB_d blocks (fAB NULL for the mean/variance sums).  partial: [n_blocks][nq][2], one deterministic partial
@@ -249,6 +267,23 @@ int pem_coupled_system_loglik_f64_dev(size_t n, double torr2pa, double radius, c
                                       const double* sigma_cex, int n_cond, int n_rec, const double* rec, const int32_t* span,
                                       int n_node, const int32_t* node, double z0, double z1, int ncells, double* V_cc,
                                       double* div_angle, double* T_c, double* loglik, uint8_t* invalid, pem_stream_t stream);
+
+/* pem_coupled_system_loglik_f64_dev's launch with the model value of every record written out instead of compared -- the
+ * predictions of the reference's validation step (scripts/pem_v0/monte_carlo.py:63-300, evaluated at each dataset's operating
+ * conditions and measurement locations).  Arguments as pem_coupled_system_loglik_f64_dev, `loglik` replaced by `pred`,
+ * `ld_pred` (>= n_rec).  Sample i = d * n_cond + c (condition c = i mod n_cond) writes the model value of each record r of
+ * condition c to pred[d * ld_pred + r]: exactly the values the likelihood compares -- j_ion fma(w, j[k+1] - j[k], j[k]) on the
+ * staged profile (which never reaches HBM), the clipped V_cc, the thrust T (not T_c), u_ion fma(w, u(z_b) - u(z_a), u(z_a)).
+ * pred holds ceil(n / n_cond) rows; padding records and records of absent samples are never written.  Non-physical samples
+ * give what the model gives (NaN included): nothing is filtered.  V_cc, div_angle, T_c, invalid: optional per-sample outputs.  */
+int pem_coupled_system_predict_f64_dev(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a,
+                                       const double* T_e, const double* V_vac, const double* Pstar, const double* P_T,
+                                       const double* mdot_a, const double* a_1, const double* c0, const double* c1,
+                                       const double* c2, const double* c3, const double* c4, const double* c5,
+                                       const double* sigma_cex, int n_cond, int n_rec, const double* rec, const int32_t* span,
+                                       int n_node, const int32_t* node, double z0, double z1, int ncells, double* V_cc,
+                                       double* div_angle, double* T_c, double* pred, size_t ld_pred, uint8_t* invalid,
+                                       pem_stream_t stream);
 
 /* pem_coupled_f64_dev + pem_svd_compress_f64_dev in one launch: latent[i][r] = sum_k norm(j_ion[i][k]) basis[k][r]
  * accumulated in the registers of the angle loop, one lane per sample (csrc/pem_latent.hip) -- the profile is neither
