@@ -18,6 +18,7 @@ NANGLE = 91
 FUSED_LATENT_MAX_RANK = 8     # PEM_FUSED_LATENT_MAX_RANK (include/pem_hip.h): latents the fused model -> compression launch keeps
 FUSED_SYSTEM_MAX_RECORDS = 1024   # PEM_FUSED_SYSTEM_MAX_RECORDS: records (and conditions) of the fused multi-QoI likelihood's LDS table
 SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of that table
+SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI groups of pem_sobol_sweep_f64_dev
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -91,6 +92,8 @@ SIGNATURES = {
     'pem_coupled_f32_dev': (C.c_int, [_sz, C.c_float, C.c_float, _dp, _sz, _dp, _sz, _dp, _dp]),
     'pem_saltelli_f32_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, C.c_float, C.c_float, _dp, _dp, C.c_int, _dp]),
     'pem_saltelli_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, _dp]),
+    'pem_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, _f8, _f8, _f8, _f8, _f8, C.c_int,
+                                          _dp, _dp, _dp, _dp, C.c_int, _dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

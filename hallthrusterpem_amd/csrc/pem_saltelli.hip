@@ -24,6 +24,7 @@
 #include "pem_model.h"
 #include "pem_model_f32.h"
 #include "pem_philox.h"
+#include "pem_wave.h"
 
 namespace {
 
@@ -168,34 +169,6 @@ __device__ __forceinline__ void design_row(const SaltelliArg& s, const int* lds_
     }
 }
 
-// Sum eight per-lane values over the 64 lanes of a wave, TRANSPOSING on the way: after the three halving steps each
-// lane carries one of the eight sums, so the whole reduction costs 4 + 2 + 1 + 3 = 10 additions (and shuffles) instead
-// of 8 x 6.  On return lane l holds the wave total of v[4 (l & 1) + 2 ((l >> 1) & 1) + ((l >> 2) & 1)].
-__device__ __forceinline__ double wave_sum8(const double (&v)[8], int lane) {
-    double w4[4], w2[2], w;
-    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double send = b0 ? v[k] : v[k + 4], keep = b0 ? v[k + 4] : v[k];
-        w4[k] = keep + __shfl_xor(send, 1);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double send = b1 ? w4[k] : w4[k + 2], keep = b1 ? w4[k + 2] : w4[k];
-        w2[k] = keep + __shfl_xor(send, 2);
-    }
-    {
-        const double send = b2 ? w2[0] : w2[1], keep = b2 ? w2[1] : w2[0];
-        w = keep + __shfl_xor(send, 4);
-    }
-    w += __shfl_xor(w, 8);
-    w += __shfl_xor(w, 16);
-    w += __shfl_xor(w, 32);
-    return w;
-}
-// which of the eight values lane l ends up with
-__device__ __forceinline__ int wave_sum8_slot(int lane) { return 4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1); }
-
 // partial: [gridDim.x][2 + 2 nv][NQ]: rows 0,1 = sum fA + fB, sum fA^2 + fB^2; rows 2+2j, 3+2j = sum fB (fAB_j - fA),
 // sum (fA - fAB_j)^2 for varied input j.  flags: [gridDim.x][2] = non-physical thruster results (T < 0 or I_B0 < 0,
 // thruster.py:490-493) and invalid plume samples among all evaluations.
@@ -227,7 +200,7 @@ void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
     for (int i = threadIdx.x; i < 4 * (NIN + 1) * 8; i += 256) (&acc[0][0][0])[i] = 0.0;
     __syncthreads();
     const int nv = s.nv;
-    const int my_slot = wave_sum8_slot(lane);
+    const int my_slot = pem::wave_sum8_slot(lane);
     unsigned int bad_thruster = 0, bad_plume = 0;
     // every wave runs the same number of iterations (the reductions inside need all 64 lanes): lanes past n evaluate
     // the last sample and contribute zeros
@@ -285,13 +258,13 @@ void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
 #pragma unroll
                 for (int q = 0; q < 6; ++q) v[q] = 0.0;
             }
-            const double tot = wave_sum8(v, lane);
+            const double tot = pem::wave_sum8(v, lane);
             if (lane < 8) acc[wave][e - 1][my_slot] += tot;   // lanes 0..7 carry the eight sums, one each
         }
     }
     {
         double v[8] = {(double)bad_thruster, (double)bad_plume, 0, 0, 0, 0, 0, 0};
-        const double tot = wave_sum8(v, lane);
+        const double tot = pem::wave_sum8(v, lane);
         if (lane < 8 && my_slot < 2) bad[wave][my_slot] = (unsigned int)tot;
     }
     __syncthreads();

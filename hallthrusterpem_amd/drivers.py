@@ -730,3 +730,112 @@ def sample_plume_without_spikes(n: int, seed: int = 0, threshold: float = 200.0,
         redraw = sampling.Design(priors=pri, names=PLUME_INPUTS, seed=seed, stream=2 * (attempt + 1)).sample(n, device=dev)
         x[:, pending] = redraw[:, pending]
     raise RuntimeError(f'{pending.numel()} samples still exceed {threshold} A/m^2 after {max_rounds} rounds')
+
+
+# ------------------------------------------------------------------------------------------- Sobol' indices over a pressure sweep
+def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'), seed: int = 0, spike_threshold: float = 200.0,
+                clip_percentile: float | None = 99.0, l_ch: float = 0.025, uion_grid=None, max_attempts: int = 64, device=None):
+    """First-order and total Sobol' indices, with standard errors, of V_cc, thrust T, ion velocity uion at z = l_ch and ion
+    current density jion at gamma = 0 over a sweep of background pressures: the study of scripts/pem_v0/sobol.py:46-118.
+
+    The study (`hallthrusterpem_amd.sobol`): per QoI group only the inputs of the component that produces it are varied --
+    Cathode (V_cc): P_b T_e V_vac Pstar P_T;  Thruster (T, uion): P_b mdot_a T_e a_1, the thruster test double's share of the
+    YAML Thruster's exogenous inputs (u_n, l_t, a_2, dz, z0, p0 belong to HallThruster.jl and are absent here);  Plume (jion):
+    P_b c0..c5 sigma_cex, the plume alone at I_B0 = 4 A, r = 1 m.  Every other input is pinned at `sobol.PEM_V0_NOMINAL`.  At
+    pressure p, P_b is Relative(20) around p and mdot_a Relative(3) around 5e-6, READ AS uniform on nominal * (1 +- x / 100)
+    intersected with the YAML domain (an assumption: amisc is absent); the calibration inputs keep their priors.
+
+    One fused fp64 launch per group covers every pressure (`pem_sobol_sweep_f64_dev`, csrc/pem_sobol_sweep.hip); only the
+    groups the requested QoIs need are launched.  Plume rows whose j_ion profile reaches `spike_threshold` anywhere are
+    redrawn (at most `max_attempts` draws; a row never accepted raises), and with `clip_percentile` every jion evaluation at
+    pressure p is clipped at thr_p, the percentile (numpy 'linear') of the accepted A and B rows' jion at p, found by a
+    pre-pass of the same launch and `column_percentiles`.  uqtils clips each model call at its own percentile; one threshold
+    per pressure over the pooled A and B rows is this project's choice.  clip_percentile=None skips the clip and the pre-pass.
+
+    Estimators per pressure, Var pooled over the A and B evaluations, t1 = fB (fAB_i - fA), t2 = (fA - fAB_i)^2:
+        S1_i = mean(t1) / Var        ST_i = mean(t2) / (2 Var)
+        se(S1_i) = sqrt((mean(t1^2) - mean(t1)^2) / N) / Var,   se(ST_i) the same of t2 over 2 Var.
+    Single GPU, fp64 only: sharding over a process group and an fp32 model are not provided.
+
+    Returns {qoi: {'S1', 'ST', 'S1_se', 'ST_se': (P, d) float64 tensors, 'inputs': names, 'mean', 'var': (P,)}, 'P_b': (P,)
+    numpy array, 'evaluations', 'non_physical', 'invalid': ints}; res['jion'] also carries 'clip' ((P,) tensor or None),
+    'rejected' ((P,) numpy int64, rejected draws per pressure) and 'j0' (the pre-pass's (P, 2 N) tensor, or None)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib, constants
+    from . import sobol as study
+    from .likelihood import UION_GRID
+    qois = (qois,) if isinstance(qois, str) else tuple(qois)
+    for q in qois:
+        if q not in study.QOIS:
+            raise ValueError(f'unknown QoI {q!r}: the study has {study.QOIS}')
+    if not qois or len(set(qois)) != len(qois):
+        raise ValueError(f'a non-empty list of distinct QoIs is needed, got {qois}')
+    n_base = int(n_base)
+    if n_base < 1:
+        raise ValueError(f'n_base must be at least 1, got {n_base}')
+    pb = np.atleast_1d(np.asarray(study.DEFAULT_PRESSURES if pressures is None else pressures, dtype=np.float64))
+    lo, hi = study.DOMAINS['P_b']
+    if pb.ndim != 1 or pb.size == 0:
+        raise ValueError('pressures must be a non-empty 1-d sequence')
+    if not np.all(np.isfinite(pb) & (pb >= lo) & (pb <= hi)):
+        raise ValueError(f'pressures must lie inside the P_b domain [{lo}, {hi}] Torr, got {pb}')
+    if clip_percentile is not None and not 0.0 <= float(clip_percentile) <= 100.0:
+        raise ValueError(f'clip_percentile must be in [0, 100] or None, got {clip_percentile}')
+    if int(max_attempts) < 1:
+        raise ValueError('max_attempts must be at least 1')
+    _, uion_z = study.uion_node(float(l_ch), UION_GRID if uion_grid is None else uion_grid)
+    groups = [g for g in study.GROUPS if any(study.QOI_GROUP[q] == g for q in qois)]
+
+    lib = _lib.load()
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    n_p = pb.size
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                        # noqa: E731
+    res = {'P_b': pb, 'evaluations': 0, 'non_physical': 0, 'invalid': 0}
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        for g in groups:
+            gid = study.GROUPS.index(g)
+            names = study.GROUP_INPUTS[g]
+            nv, nq = len(names), len(study.GROUP_QOIS[g])
+            rows = 2 + 4 * nv
+            kind, a, b = (torch.as_tensor(t, device=dev) for t in study.prior_tables(pb, g))
+            # workgroups resident at once over all pressures: 2 per CU for the Plume instantiation (256 registers), 4 otherwise
+            n_blocks = max(1, min(-(-n_base // 256), -(-cus * (2 if g == 'Plume' else 4) // n_p)))
+            partial = torch.empty((n_p, n_blocks, rows, nq), dtype=torch.float64, device=dev)
+            flags = torch.empty((n_p, n_blocks, 4), dtype=torch.int64, device=dev)
+
+            def launch(clip, j0):
+                _lib.check(lib.pem_sobol_sweep_f64_dev(gid, n_base, 0, int(seed), n_p, ptr(kind), ptr(a), ptr(b), constants.TORR_2_PA,
+                                                       study.PLUME_RADIUS, study.PLUME_I_B0, uion_z, float(spike_threshold),
+                                                       int(max_attempts), ptr(clip), ptr(j0), ptr(partial), ptr(flags), n_blocks, stream))
+            clip = j0 = None
+            if g == 'Plume' and clip_percentile is not None:
+                j0 = torch.empty((n_p, 2 * n_base), dtype=torch.float64, device=dev)
+                launch(None, j0)
+                clip = column_percentiles(j0.T, float(clip_percentile)).contiguous()
+            launch(clip, None)
+            s = partial.sum(dim=1)                                        # [P][rows][nq]
+            cnt = flags.sum(dim=1).cpu().numpy()                          # [P][4]
+            if cnt[:, 3].any():
+                raise RuntimeError(f'{int(cnt[:, 3].sum())} plume rows still reach {spike_threshold} A/m^2 after {max_attempts} draws')
+            mean = s[:, 0] / (2 * n_base)
+            var = s[:, 1] / (2 * n_base) - mean * mean
+            m1, m1sq, m2, m2sq = (s[:, 2 + w::4] / n_base for w in range(4))     # [P][nv][nq] each
+            for k, q in enumerate(study.GROUP_QOIS[g]):
+                if q not in qois:
+                    continue
+                v = var[:, k:k + 1]
+                res[q] = {'S1': m1[..., k] / v, 'ST': m2[..., k] / (2 * v),
+                          'S1_se': torch.sqrt((m1sq[..., k] - m1[..., k] ** 2) / n_base) / v,
+                          'ST_se': torch.sqrt((m2sq[..., k] - m2[..., k] ** 2) / n_base) / (2 * v),
+                          'inputs': names, 'mean': mean[:, k], 'var': var[:, k]}
+            if g == 'Plume' and 'jion' in res:
+                res['jion'].update(clip=clip, rejected=cnt[:, 2].astype(np.int64), j0=j0)
+            res['evaluations'] += n_base * n_p * (nv + 2)
+            res['non_physical'] += int(cnt[:, 0].sum())
+            res['invalid'] += int(cnt[:, 1].sum())
+    return res

@@ -552,6 +552,38 @@ int pem_saltelli_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uin
                          const double* a, const double* b, int n_varied, const int32_t* varied, double torr2pa,
                          double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
 
+/* ---- the Sobol' study over a pressure sweep (csrc/pem_sobol_sweep.hip) --------------------------------------------------
+ * scripts/pem_v0/sobol.py:46-118 (compute_indices; uqtils sobol_sa, third-party: parity UNPINNED): per QoI group only the
+ * exogenous inputs of the component that produces it are varied, every other input sits at a pin, at each of n_p background
+ * pressures.  ONE launch covers one group at every pressure (blockIdx.y = pressure):
+ *   group PEM_SWEEP_CATHODE   QoI V_cc                     varied P_b T_e V_vac Pstar P_T       (input rows 0 2 3 4 5)
+ *         PEM_SWEEP_THRUSTER  QoIs T, u_ion(uion_z)        varied P_b mdot_a T_e a_1            (input rows 0 6 2 7)
+ *         PEM_SWEEP_PLUME     QoI j_ion(gamma = 0)         varied P_b c0..c5 sigma_cex          (input rows 0 8..14)
+ *   The Thruster group runs cathode -> thruster test double (u_ion = v_exh / (1 + exp(-100 (uion_z - 0.04))),
+ *   sim_hallthruster.jl:46-47); the Plume group runs the plume alone at I_B0 = i_b0 and r = radius.
+ * kind, a, b: DEVICE arrays [n_p][15] (rows as pem_coupled_f64_dev's inputs), the PEM_DIST_* prior of every input at each
+ *   pressure; for an input outside the group's varied set only a[p][d] is read: the value it is pinned at.
+ * Streams: attempt k of row r (0: A, 1: B) of group g at pressure p is stream 2 * 3 * n_p * k + 2 (g n_p + p) + r of the
+ *   counter-based design (seed; base samples first_index ..): the numbers of pem_sample_f64_dev for that stream and table.
+ *   Only the Plume group makes attempts k > 0: a row whose j_ion profile reaches spike_threshold anywhere on the 91-angle
+ *   grid is redrawn, at most max_attempts times (sobol.py:50-66).  The accepted set does not depend on the launch shape.
+ * clip (Plume only, DEVICE [n_p] or NULL): every j_ion(0) of pressure p -- A, B and AB -- is min(j, clip[p]) (sobol.py:82-89).
+ * j0_out (Plume only, DEVICE [n_p][2 n_base] or NULL): the PRE-PASS; j_ion(0) of the accepted rows A (at [p][i]) and B
+ *   (at [p][n_base + i]), unclipped, is written and no estimator sums are formed (partial may be NULL).
+ * partial: DEVICE [n_p][n_blocks][2 + 4 nv][nq] fp64, one deterministic partial per workgroup.  Rows: sum fA + fB,
+ *   sum fA^2 + fB^2, then per varied input j: sum t1, sum t1^2, sum t2, sum t2^2 with t1 = fB (fAB_j - fA),
+ *   t2 = (fA - fAB_j)^2.  nq = 2 (T, u_ion) for the Thruster group, 1 otherwise.
+ * flags: DEVICE [n_p][n_blocks][4] counts: non-physical thruster results (thruster.py:490-493, T < 0 or I_B0 < 0) and invalid
+ *   plume samples (plume.py:105) among the evaluations, rejected draws, rows never accepted within max_attempts.           */
+#define PEM_SWEEP_CATHODE 0
+#define PEM_SWEEP_THRUSTER 1
+#define PEM_SWEEP_PLUME 2
+#define PEM_SWEEP_MAX_PRESSURES 65535
+int pem_sobol_sweep_f64_dev(int group, size_t n_base, uint64_t first_index, uint64_t seed, int n_p, const int32_t* kind,
+                            const double* a, const double* b, double torr2pa, double radius, double i_b0, double uion_z,
+                            double spike_threshold, int max_attempts, const double* clip, double* j0_out, double* partial,
+                            uint64_t* flags, int n_blocks, pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
