@@ -19,6 +19,8 @@ FUSED_LATENT_MAX_RANK = 8     # PEM_FUSED_LATENT_MAX_RANK (include/pem_hip.h): l
 FUSED_SYSTEM_MAX_RECORDS = 1024   # PEM_FUSED_SYSTEM_MAX_RECORDS: records (and conditions) of the fused multi-QoI likelihood's LDS table
 SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of that table
 SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI groups of pem_sobol_sweep_f64_dev
+DE_MAX_POP, DE_MAX_DIM = 1024, 16   # PEM_DE_MAX_POP / PEM_DE_MAX_DIM: population and dimensions of pem_de_step_f64_dev
+DE_BEST1BIN, DE_RAND1BIN = 0, 1     # PEM_DE_*: its strategies
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -94,6 +96,8 @@ SIGNATURES = {
     'pem_saltelli_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, _dp]),
     'pem_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, _f8, _f8, _f8, _f8, _f8, C.c_int,
                                           _dp, _dp, _dp, _dp, C.c_int, _dp]),
+    'pem_de_step_f64_dev': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, _f8, _dp, _dp, _dp, _dp, _dp, _dp,
+                                      _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

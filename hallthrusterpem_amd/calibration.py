@@ -70,8 +70,10 @@ class BatchedPosterior:
     the prior on the device, marginalisation, graph capture.  A subclass builds its likelihood and runs it (`_run_loglik`)."""
 
     def _setup(self, theta_names, operating, make_likelihood, n_chains, n_nuisance, priors, seed, discharge, sweep_radius,
-               fresh_nuisance):
+               fresh_nuisance, shared_nuisance=False):
         import torch
+        if shared_nuisance and fresh_nuisance:
+            raise ValueError('shared_nuisance needs fresh_nuisance=False: shared draws are the same on every evaluation')
         self.names = tuple(theta_names)
         for k in self.names:
             if k not in COUPLED_INPUTS or k in OPERATING:
@@ -94,7 +96,11 @@ class BatchedPosterior:
         self.op_rows = [COUPLED_INPUTS.index(k) for k in OPERATING]
         self.discharge = None if discharge is None else (float(discharge[0]), float(discharge[1]))
         self.fresh = bool(fresh_nuisance)
+        self.shared = bool(shared_nuisance)
         self.first_index = 0
+        if self.shared:         # draws 0 .. M Ne - 1 of the design, broadcast over the K rows on every evaluation
+            self._shared_block = self.design.fill(torch.empty((len(COUPLED_INPUTS), self.M * self.Ne), dtype=torch.float64,
+                                                              device=self.device))
         self.loglik = torch.empty(self.n, dtype=torch.float64, device=self.device)
         self._view = lambda t: t.view(self.K, self.M, self.Ne)
         # few launches per evaluation (every one is latency-bound): row scatter indices and the prior table on device
@@ -114,10 +120,13 @@ class BatchedPosterior:
     # ------------------------------------------------------------------------------------------------ evaluation
     def assemble_inputs(self, theta):
         """Fill the batch: nuisance draws for everything, then the operating columns and theta broadcast over them."""
-        self.design.fill(self.batch.inputs, first_index=self.first_index)
-        if self.fresh:
-            self.first_index += self.n
         x = self.batch.inputs.view(len(COUPLED_INPUTS), self.K, self.M, self.Ne)
+        if self.shared:
+            x.copy_(self._shared_block.view(len(COUPLED_INPUTS), 1, self.M, self.Ne).expand(-1, self.K, -1, -1))
+        else:
+            self.design.fill(self.batch.inputs, first_index=self.first_index)
+            if self.fresh:
+                self.first_index += self.n
         x.index_copy_(0, self._op_idx, self._op_vals.expand(-1, self.K, self.M, -1))
         x.index_copy_(0, self._theta_idx, theta.T[:, :, None, None].expand(-1, -1, self.M, self.Ne))
 
@@ -187,15 +196,18 @@ class BatchedPosterior:
 class JionPosterior(BatchedPosterior):
     def __init__(self, theta_names, operating, alpha, y, std, n_chains: int, n_nuisance: int = 100, priors=None,
                  seed: int = 0, discharge=(4.5, 0.2), sweep_radius: float = 1.0, fresh_nuisance: bool = True,
-                 device=None):
+                 device=None, shared_nuisance: bool = False):
         """theta_names: calibrated inputs (subset of the 15 coupled inputs, not operating ones);
         operating: (Ne, 3) array of `P_b [Torr], V_a [V], mdot_a [kg/s]` per experiment;
         alpha, y, std: (Ne, Na) measurement angles [rad], current densities and standard deviations at `sweep_radius`;
         discharge: (I_d, sigma) of the extra discharge-current weight (mcmc.py:48-49,102-104) or None;
         fresh_nuisance: new nuisance draws on every evaluation (as the reference) -- inside a captured graph the
-        draws are whatever was recorded (common random numbers)."""
+        draws are whatever was recorded (common random numbers);
+        shared_nuisance: every row uses draws 0 .. M Ne - 1 of the design, so that a value depends on theta, seed, M and the
+        data and not on the row or on K (what an optimizer or a finite-difference Hessian comparing rows needs); requires
+        fresh_nuisance=False.  Otherwise row k uses draws k M Ne .. (k + 1) M Ne - 1."""
         self._setup(theta_names, operating, lambda: JionLikelihood(alpha, y, std, device=device), n_chains, n_nuisance, priors,
-                    seed, discharge, sweep_radius, fresh_nuisance)
+                    seed, discharge, sweep_radius, fresh_nuisance, shared_nuisance)
 
     def _run_loglik(self):
         self.batch.run_loglik(self.lik, out=self.loglik)
@@ -203,17 +215,17 @@ class JionPosterior(BatchedPosterior):
 
 class SystemPosterior(BatchedPosterior):
     def __init__(self, theta_names, likelihood: SystemLikelihood, n_chains: int, n_nuisance: int = 100, priors=None,
-                 seed: int = 0, discharge=(4.5, 0.2), fresh_nuisance: bool = True):
+                 seed: int = 0, discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False):
         """The posterior of the reference's `System` calibration (mcmc.py:28-130): V_cc, thrust, ion velocity and ion current
         density, each from its own dataset (`likelihood.SystemLikelihood`, whose conditions are the Ne operating conditions
         here), evaluated by ONE fused launch (`pem_coupled_system_loglik_f64_dev`) per evaluation.  The interface of
-        `JionPosterior`; theta_names, n_chains, n_nuisance, priors, seed, fresh_nuisance as there.
+        `JionPosterior`; theta_names, n_chains, n_nuisance, priors, seed, fresh_nuisance, shared_nuisance as there.
         discharge: (I_d, sigma) of the discharge-current weight added for every condition, or None; dropped when the
         likelihood's component is 'Cathode' (mcmc.py:100-101)."""
         if not likelihood.use_discharge:
             discharge = None
         self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, priors, seed, discharge,
-                    likelihood.sweep_radius, fresh_nuisance)
+                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance)
 
     def _run_loglik(self):
         self.batch.run_system_loglik(self.lik, out=self.loglik)

@@ -1,0 +1,343 @@
+"""Where to start the chains, and with what proposal: maximum a posteriori search, Laplace covariance and 1-D slices.
+
+Restates the steps of scripts/pem_v0/mcmc.py that come before `run_mcmc`:
+
+    run_mle(optimizer='evolution')   mcmc.py:170-231   `DifferentialEvolution`: scipy's differential_evolution (best1bin /
+                                                       rand1bin, dithered F, CR 0.7, deferred updating) with the whole
+                                                       population evaluated as the rows of ONE posterior launch
+    run_laplace / show_laplace       mcmc.py:234-265   `hessian` (central differences, 2 d^2 + 1 points in one call) and
+                                                       `Laplace` (cov = pinv(-H), nearest positive-definite fall-back, draws)
+    pdf_slice                        mcmc.py:132-148   `slices`: log prior, likelihood and posterior along every axis
+
+The search runs over the prior's quantile cube u in (0, 1)^d (theta = the prior transform of u, `pem::transform` of
+csrc/pem_philox.h): log-uniform inputs mutate in log space, normals need no bounds.  One generation is one launch of
+`pem_de_step_f64_dev` (csrc/pem_de.hip: selection, best member, convergence statistic and the next trials) followed by the
+caller's `f`; with `use_graph` the two are one hipGraph replay.  `f` is what an optimizer compares across rows, so a
+`JionPosterior` / `SystemPosterior` passed here is built with `shared_nuisance=True` (the same nuisance draws in every row).
+"""
+import ctypes as C
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .calibration import capture_graph
+from .sampling import LOGUNIFORM, NORMAL, PEM_V0_PRIORS, UNIFORM, Design, Prior
+
+STRATEGIES = {'best1bin': _lib.DE_BEST1BIN, 'rand1bin': _lib.DE_RAND1BIN}
+
+
+def _table(names, priors):
+    priors = PEM_V0_PRIORS if priors is None else priors
+    for k in names:
+        if k not in priors:
+            raise KeyError(f"no prior for '{k}'")
+    pr = [priors[k] for k in names]
+    return (np.ascontiguousarray([p.kind for p in pr], dtype=np.int32), np.ascontiguousarray([p.a for p in pr], dtype=np.float64),
+            np.ascontiguousarray([p.b for p in pr], dtype=np.float64))
+
+
+def support(prior: Prior):
+    """(lo, hi) of a prior's support; a normal's is taken as mean +- 3 standard deviations"""
+    if prior.kind == UNIFORM:
+        return prior.a, prior.b
+    if prior.kind == LOGUNIFORM:
+        return 10.0 ** prior.a, 10.0 ** prior.b
+    return prior.a - 3.0 * prior.b, prior.a + 3.0 * prior.b
+
+
+@dataclass
+class DEResult:
+    theta: np.ndarray        # (d,) the best member
+    u: np.ndarray            # (d,) its quantiles
+    value: float             # f there
+    generations: int         # generations evaluated after the initial population
+    converged: bool          # std(f) <= atol + tol |mean(f)| was met
+    history: np.ndarray      # (generations + 1,) best value of the initial population and of every generation
+
+
+class DifferentialEvolution:
+    """scipy's `differential_evolution(f, bounds, strategy, popsize=15, mutation=(0.5, 1), recombination=0.7, tol=0.01,
+    updating='deferred', vectorized=True)` (mcmc.py:214-216), MAXIMISING f, on the device.
+
+    f: callable (P, d) float64 device tensor -> (P,) values, P = popsize * d (`.P`), like `DRAM`'s `log_posterior`:
+       `post.log_posterior` or `post.log_likelihood` of a posterior with n_chains = P and shared_nuisance=True.
+    names, priors: the searched inputs and their priors (the search is over their quantiles).
+    mutation: F, or (lo, hi) for F ~ U(lo, hi) drawn once per generation.  seed: the Philox key of every draw.
+    The initial population is a Latin hypercube of u (`Design.fill(method='lhs')` over U(0, 1)), as scipy's default init.
+    use_graph: a generation (the DE launch and f's launches) is one hipGraph replay on one stream."""
+
+    def __init__(self, f, names, priors=None, popsize: int = 15, mutation=(0.5, 1.0), recombination: float = 0.7,
+                 strategy: str = 'best1bin', tol: float = 0.01, atol: float = 0.0, seed: int = 0, use_graph: bool = False,
+                 device=None):
+        self.names = tuple(names)
+        self.d = len(self.names)
+        if len(set(self.names)) != self.d or self.d < 1:
+            raise ValueError('names must be distinct and non-empty')
+        if self.d > _lib.DE_MAX_DIM:
+            raise ValueError(f'at most {_lib.DE_MAX_DIM} searched inputs (got {self.d})')
+        self.P = int(popsize) * self.d
+        if not 4 <= self.P <= _lib.DE_MAX_POP:
+            raise ValueError(f'population popsize * d = {self.P} must be in [4, {_lib.DE_MAX_POP}]')
+        if strategy not in STRATEGIES:
+            raise ValueError(f"unknown strategy '{strategy}' (one of {sorted(STRATEGIES)})")
+        lo, hi = (float(mutation), float(mutation)) if np.ndim(mutation) == 0 else (float(mutation[0]), float(mutation[1]))
+        if not 0.0 <= lo <= hi <= 2.0:
+            raise ValueError('mutation must be in [0, 2], a dither (lo, hi) with lo <= hi')
+        if not 0.0 <= recombination <= 1.0:
+            raise ValueError('recombination must be in [0, 1]')
+        self.kind, self.a, self.b = _table(self.names, priors)
+        self.f, self.strategy, self.mutation, self.cr = f, STRATEGIES[strategy], (lo, hi), float(recombination)
+        self.tol, self.atol, self.seed, self.use_graph = float(tol), float(atol), int(seed), bool(use_graph)
+
+        import torch
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        self.pop_u, self.trial_u, self.theta = z(self.P, self.d), z(self.P, self.d), z(self.P, self.d)
+        self.pop_f, self.trial_f = z(self.P), z(self.P)
+        self.state, self.record = z(1, dt=torch.int64), z(3)
+        unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
+        self.u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(
+            self.P, device=self.device, method='lhs').T.contiguous()
+        self.history = z(0)
+        self._graph = None
+
+    def _launch(self, finalize: bool):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
+        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_de_step_f64_dev(
+                self.P, self.d, self.strategy, 1 if finalize else 0, self.seed, self.mutation[0], self.mutation[1], self.cr,
+                self.tol, self.atol, ptr(self.kind), ptr(self.a), ptr(self.b), p(self.pop_u), p(self.pop_f), p(self.trial_u),
+                p(self.trial_f), p(self.theta), p(self.state), p(self.record), p(self.history) if self.history.numel() else None,
+                self.history.numel(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _generation(self):
+        self._launch(False)
+        self.trial_f.copy_(self.f(self.theta))
+
+    def reset(self):
+        """Back to the initial population (the next launch evaluates it)."""
+        self.state.zero_()
+        self.trial_u.copy_(self.u0)
+
+    def _prepare(self, n_launches: int):
+        """history room for n_launches; the graph is (re)recorded when the history buffer moves"""
+        import torch
+        if self.history.numel() < n_launches:
+            self.history = torch.full((n_launches,), math.nan, dtype=torch.float64, device=self.device)
+            self._graph = None
+        if self.use_graph and self._graph is None:
+            self.reset()
+            self._graph, _ = capture_graph(self._generation, self.device)
+        self.reset()
+
+    def run(self, max_generations: int = 1000, check_every: int = 10) -> DEResult:
+        """Evaluate the initial population and at most `max_generations` generations after it; every `check_every`
+        generations the host reads the 3-double convergence record and stops once std(f) <= atol + tol |mean(f)|."""
+        import torch
+        if max_generations < 0 or check_every < 1:
+            raise ValueError('max_generations >= 0 and check_every >= 1')
+        n = int(max_generations) + 1
+        self._prepare(n)
+        converged = False
+        c = 0
+        for c in range(n):
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._generation()
+            if c >= 1 and c % check_every == 0 and self.record[2].item() == 1.0:
+                converged = True
+                break
+        self._launch(True)                     # selection of the last trials; theta = the population's
+        rec = self.record.cpu().numpy()
+        best = int(rec[1])
+        torch.cuda.synchronize(self.device)
+        return DEResult(theta=self.theta[best].cpu().numpy(), u=self.pop_u[best].cpu().numpy(), value=float(rec[0]),
+                        generations=c, converged=converged or bool(rec[2] == 1.0),
+                        history=self.history[:c + 1].cpu().numpy())
+
+
+# ----------------------------------------------------------------------------------------------------------- Laplace
+def stencil_size(d: int) -> int:
+    """rows of `hessian`'s stencil: the centre, +-h_i and +-h_i +-h_j"""
+    return 2 * d * d + 1
+
+
+def theta_steps(theta, names, priors=None, step: float = 1e-3):
+    """h_j = step * d theta_j / d u_j at theta: (b - a) uniform, theta ln10 (b - a) log-uniform, sigma / phi(z) normal"""
+    kind, a, b = _table(names, priors)
+    t = np.asarray(theta, dtype=np.float64)
+    h = np.where(kind == UNIFORM, b - a, 0.0)
+    h = np.where(kind == LOGUNIFORM, t * math.log(10.0) * (b - a), h)
+    z = np.where(kind == NORMAL, (t - a) / np.where(kind == NORMAL, b, 1.0), 0.0)
+    h = np.where(kind == NORMAL, b * math.sqrt(2.0 * math.pi) * np.exp(0.5 * z * z), h)
+    return step * h
+
+
+def stencil(theta, h):
+    """(2 d^2 + 1, d) points: the centre, then theta +- h_i e_i, then theta (+-) h_i e_i (+-) h_j e_j for i < j"""
+    t, h = np.asarray(theta, dtype=np.float64), np.asarray(h, dtype=np.float64)
+    d = t.size
+    rows = [t.copy()]
+    for i in range(d):
+        for s in (1.0, -1.0):
+            r = t.copy()
+            r[i] += s * h[i]
+            rows.append(r)
+    for i in range(d):
+        for j in range(i + 1, d):
+            for si, sj in ((1.0, 1.0), (1.0, -1.0), (-1.0, 1.0), (-1.0, -1.0)):
+                r = t.copy()
+                r[i] += si * h[i]
+                r[j] += sj * h[j]
+                rows.append(r)
+    return np.stack(rows)
+
+
+def hessian(f, theta, names, priors=None, step: float = 1e-3, device=None):
+    """Central-difference Hessian of f at theta from ONE call of f on the (2 d^2 + 1, d) stencil (`stencil`), steps
+    `theta_steps`.  f: (2 d^2 + 1, d) float64 tensor on `device` (default CPU) -> values, e.g. `post.log_posterior` of a
+    posterior with n_chains = stencil_size(d) and shared_nuisance=True.  Every stencil point must lie in the prior support."""
+    import torch
+    names = tuple(names)
+    priors_ = PEM_V0_PRIORS if priors is None else priors
+    t = np.asarray(theta, dtype=np.float64)
+    d = len(names)
+    if t.shape != (d,):
+        raise ValueError(f'theta must have one entry per name ({d})')
+    h = theta_steps(t, names, priors_, step)
+    pts = stencil(t, h)
+    for j, k in enumerate(names):
+        if priors_[k].kind == NORMAL:
+            continue
+        lo, hi = support(priors_[k])
+        if pts[:, j].min() < lo or pts[:, j].max() > hi:
+            raise ValueError(f"the Hessian stencil leaves the prior support of '{k}' ({lo:g}, {hi:g}) at {t[j]:g}: "
+                             'a MAP on a bound has no Laplace approximation there')
+    dev = torch.device('cpu') if device is None else torch.device(device)
+    v = f(torch.as_tensor(pts, device=dev))
+    v = (v.cpu().numpy() if hasattr(v, 'cpu') else np.asarray(v)).astype(np.float64)
+    f0, k = v[0], 1 + 2 * d
+    H = np.empty((d, d))
+    for i in range(d):
+        H[i, i] = (v[1 + 2 * i] - 2.0 * f0 + v[2 + 2 * i]) / (h[i] * h[i])
+    for i in range(d):
+        for j in range(i + 1, d):
+            pp, pm, mp, mm = v[k:k + 4]
+            H[i, j] = H[j, i] = (pp - pm - mp + mm) / (4.0 * h[i] * h[j])
+            k += 4
+    return H
+
+
+def is_positive_definite(A) -> bool:
+    try:
+        np.linalg.cholesky(A)
+        return True
+    except np.linalg.LinAlgError:
+        return False
+
+
+def nearest_positive_definite(A):
+    """Higham's nearest symmetric positive-definite matrix to A (Higham 1988, "Computing a nearest symmetric positive
+    semidefinite matrix"): the mean of the symmetric part and its polar factor, then a diagonal shift by the smallest
+    eigenvalue until a Cholesky factorisation succeeds.  A symmetric positive-definite A is returned unchanged."""
+    A = np.asarray(A, dtype=np.float64)
+    if np.array_equal(A, A.T) and is_positive_definite(A):
+        return A.copy()
+    B = 0.5 * (A + A.T)
+    _, s, V = np.linalg.svd(B)
+    X = 0.5 * (B + V.T @ np.diag(s) @ V)
+    X = 0.5 * (X + X.T)
+    spacing = np.spacing(np.linalg.norm(A))
+    eye = np.eye(A.shape[0])
+    k = 1
+    while not is_positive_definite(X):
+        X += eye * (-np.min(np.linalg.eigvalsh(X)) * k * k + spacing)
+        k += 1
+    return X
+
+
+class Laplace:
+    """Gaussian approximation of the posterior at its mode (run_laplace / show_laplace, mcmc.py:234-265): mean = the mode,
+    hess = the Hessian of the log posterior there, cov = pinv(-hess), replaced by its nearest positive-definite matrix when
+    it is not positive definite (`nearest_pd` records that).  The pseudo-inverse is taken in coordinates scaled by
+    |hess_ii|^-1/2 (the same matrix when hess is invertible): the parameters span twelve decades (P_T ~ 1e-5, c4 ~ 1e20),
+    and pinv's cut-off, relative to the largest singular value, would otherwise discard the directions of the large ones."""
+
+    def __init__(self, mean, hess):
+        self.mean = np.asarray(mean, dtype=np.float64).copy()
+        self.hess = np.asarray(hess, dtype=np.float64).copy()
+        dg = np.abs(np.diag(self.hess))
+        s = np.where((dg > 0) & np.isfinite(dg), 1.0 / np.sqrt(np.where(dg > 0, dg, 1.0)), 1.0)
+        cov = s[:, None] * np.linalg.pinv(-(s[:, None] * self.hess * s[None, :])) * s[None, :]
+        cov = 0.5 * (cov + cov.T)
+        self.nearest_pd = not is_positive_definite(cov)
+        self.cov = nearest_positive_definite(cov) if self.nearest_pd else cov
+
+    @classmethod
+    def fit(cls, f, mean, names, priors=None, step: float = 1e-3, device=None):
+        """`hessian(f, mean, ...)` and the approximation built from it"""
+        return cls(mean, hessian(f, mean, names, priors, step=step, device=device))
+
+    @property
+    def std(self):
+        return np.sqrt(np.diag(self.cov))
+
+    def sample(self, n: int, seed: int = 0):
+        """(n, d) draws of N(mean, cov)"""
+        L = np.linalg.cholesky(self.cov)
+        return self.mean + np.random.default_rng(seed).standard_normal((int(n), self.mean.size)) @ L.T
+
+    def dram_start(self):
+        """(theta0, cov0) for `calibration.DRAM`"""
+        return self.mean.copy(), self.cov.copy()
+
+
+# ------------------------------------------------------------------------------------------------------------ slices
+def slice_points(names, x0, n_steps: int = 15, bounds=None, priors=None):
+    """(d n_steps, d) rows: axis j of x0 swept over bounds[j] (default the prior support; geometric steps for a log-uniform
+    prior), the other entries held at x0.  Bounds outside the support are refused."""
+    names = tuple(names)
+    priors = PEM_V0_PRIORS if priors is None else priors
+    x0 = np.asarray(x0, dtype=np.float64)
+    d = len(names)
+    if x0.shape != (d,) or n_steps < 2:
+        raise ValueError(f'x0 must have one entry per name ({d}) and n_steps >= 2')
+    rows = np.repeat(x0[None], d * n_steps, axis=0)
+    for j, k in enumerate(names):
+        p = priors[k]
+        lo, hi = support(p)
+        blo, bhi = (lo, hi) if bounds is None else (float(bounds[j][0]), float(bounds[j][1]))
+        if not (blo < bhi) or (p.kind != NORMAL and (blo < lo or bhi > hi)):
+            raise ValueError(f"slice bounds ({blo:g}, {bhi:g}) of '{k}' are not an interval inside its prior support "
+                             f'({lo:g}, {hi:g})')
+        grid = np.geomspace(blo, bhi, n_steps) if p.kind == LOGUNIFORM else np.linspace(blo, bhi, n_steps)
+        rows[j * n_steps:(j + 1) * n_steps, j] = grid
+    return rows
+
+
+def slices(post, x0, n_steps: int = 15, bounds=None):
+    """1-D slices of the log prior, log likelihood and log posterior through x0 (pdf_slice, mcmc.py:132-148): a dict of
+    (d, n_steps) arrays 'grid', 'prior', 'likelihood', 'posterior'.  post: a posterior with n_chains = d n_steps and
+    shared_nuisance=True; one prior launch and one likelihood launch over all rows."""
+    import torch
+    d = len(post.names)
+    if not getattr(post, 'shared', False):
+        raise ValueError('slices compare rows: build the posterior with shared_nuisance=True')
+    if post.K != d * n_steps:
+        raise ValueError(f'the posterior has {post.K} rows, the slices need d * n_steps = {d * n_steps}')
+    rows = slice_points(post.names, x0, n_steps, bounds, post.priors)
+    theta = torch.as_tensor(rows, device=post.device)
+    lp = post.log_prior(theta)
+    ll = post.log_likelihood(theta)
+    # the marginalisation kernel's rule for the posterior: prior + likelihood where both are usable, -inf elsewhere
+    lpost = torch.where(torch.isfinite(lp) & ~torch.isnan(ll), lp + ll, torch.full_like(lp, -math.inf))
+    grid = np.stack([rows[j * n_steps:(j + 1) * n_steps, j] for j in range(d)])
+    out = {'grid': grid}
+    for k, v in (('prior', lp), ('likelihood', ll), ('posterior', lpost)):
+        out[k] = v.cpu().numpy().reshape(d, n_steps)
+    return out

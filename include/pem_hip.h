@@ -584,6 +584,30 @@ int pem_sobol_sweep_f64_dev(int group, size_t n_base, uint64_t first_index, uint
                             double spike_threshold, int max_attempts, const double* clip, double* j0_out, double* partial,
                             uint64_t* flags, int n_blocks, pem_stream_t stream);
 
+/* ---- differential evolution over the prior's quantile cube (csrc/pem_de.hip, hallthrusterpem_amd/optimize.py) ---------------
+ * Stands in for run_mle(optimizer='evolution') (scripts/pem_v0/mcmc.py:170-231): scipy's differential_evolution semantics
+ * (best1bin or rand1bin, F ~ U(mut_lo, mut_hi) once per generation, binomial crossover with probability cr and one forced
+ * dimension, deferred updating, components leaving (0, 1) redrawn uniformly), MAXIMISING f over u in (0, 1)^ndim; theta =
+ * the prior transform of u (kind/a/b: HOST arrays of ndim, as pem_sample_f64_dev).  One workgroup, one thread per member.
+ * DEVICE arrays: pop_u, trial_u, theta [pop][ndim]; pop_f, trial_f [pop]; state [1]; record [3]; history [history_len] or NULL.
+ * state = g counts the launches so far (the caller zeroes it; a captured graph advances it on every replay):
+ *   g == 0  trial_u holds the initial design: it is clamped into [2^-53, 1 - 2^-53] and theta = its transform.
+ *   g >= 1  1. the trials (u in trial_u, values in trial_f) replace the members they beat (all of them when g == 1);
+ *           NaN and -inf never beat anything.  2. record = {best value, best index, converged}: the largest value (NaN / -inf
+ *           rank as -inf; ties to the lowest index) and std(f) <= atol + tol |mean(f)| (sums in a fixed order; a non-finite
+ *           member is never converged); history[g - 1] = best value when g - 1 < history_len.  3. unless finalize, the next
+ *           trials from Philox4x32-10(counter = (member, g, purpose, pair), key = seed) into trial_u and their transform
+ *           into theta, and state = g + 1.  With finalize, theta = the transform of the population and state is kept.
+ * 4 <= pop <= PEM_DE_MAX_POP, 1 <= ndim <= PEM_DE_MAX_DIM.                                                                 */
+#define PEM_DE_MAX_POP 1024
+#define PEM_DE_MAX_DIM 16
+#define PEM_DE_BEST1BIN 0
+#define PEM_DE_RAND1BIN 1
+int pem_de_step_f64_dev(int pop, int ndim, int strategy, int finalize, uint64_t seed, double mut_lo, double mut_hi, double cr,
+                        double tol, double atol, const int32_t* kind, const double* a, const double* b, double* pop_u,
+                        double* pop_f, double* trial_u, const double* trial_f, double* theta, uint64_t* state, double* record,
+                        double* history, size_t history_len, pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
