@@ -59,7 +59,7 @@ SIGNATURES = {
     'pem_predictive_noise_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _sz, _dp]),
     'pem_coupled_latent_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp] + [_dp] * 4 + [_dp]),
     'pem_loglik_marginal_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, _f8, _f8, _dp, _dp, _dp]),
-    'pem_log_prior_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    'pem_log_prior_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     'pem_jion_loglik_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int] + [_dp] * 6 + [_dp]),
     'pem_svd_compress_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, _f8, _dp, _dp, _dp, _dp]),
     'pem_svd_reconstruct_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, _f8, _dp, _dp, _dp, _dp]),

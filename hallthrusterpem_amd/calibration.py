@@ -111,6 +111,9 @@ class BatchedPosterior:
         self._kind = np.ascontiguousarray([q.kind for q in pr], dtype=np.int32)
         self._a = np.ascontiguousarray([q.a for q in pr], dtype=np.float64)
         self._b = np.ascontiguousarray([q.b for q in pr], dtype=np.float64)
+        # the log-uniform supports as log_prior decides them (10.0 ** a, 10.0 ** b on the host), for the device to compare against
+        self._lo = np.ascontiguousarray([10.0 ** q.a if q.kind == LOGUNIFORM else q.a for q in pr], dtype=np.float64)
+        self._hi = np.ascontiguousarray([10.0 ** q.b if q.kind == LOGUNIFORM else q.b for q in pr], dtype=np.float64)
         self._lp = torch.empty(self.K, dtype=torch.float64, device=self.device)
         self._out = torch.empty(self.K, dtype=torch.float64, device=self.device)
 
@@ -158,8 +161,8 @@ class BatchedPosterior:
         ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                                        # noqa: E731
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pem_log_prior_f64_dev(
-                theta.shape[0], len(self.names), ptr(self._kind), ptr(self._a), ptr(self._b), C.c_void_p(theta.data_ptr()),
-                C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                theta.shape[0], len(self.names), ptr(self._kind), ptr(self._a), ptr(self._b), ptr(self._lo), ptr(self._hi),
+                C.c_void_p(theta.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return out
 
     def log_posterior(self, theta, out=None):

@@ -179,9 +179,11 @@ __global__ __launch_bounds__(BLOCK) void loglik_marginal_kernel(int n_draws, int
     }
 }
 
+// lo / hi: the support of a log-uniform entry, [10^a, 10^b] as the caller rounded it.  The device's pow(10, a) is not the host's
+// 10.0 ** a (the P_b prior's edges differ by an ulp), and the support decision has to be calibration.log_prior's bit for bit.
 struct PriorTable {
     int32_t kind[PEM_SAMPLE_MAX_DIM];
-    double a[PEM_SAMPLE_MAX_DIM], b[PEM_SAMPLE_MAX_DIM];
+    double a[PEM_SAMPLE_MAX_DIM], b[PEM_SAMPLE_MAX_DIM], lo[PEM_SAMPLE_MAX_DIM], hi[PEM_SAMPLE_MAX_DIM];
 };
 
 __global__ void log_prior_kernel(long long n, int ndim, PriorTable t, const double* __restrict__ theta,
@@ -195,7 +197,7 @@ __global__ void log_prior_kernel(long long n, int ndim, PriorTable t, const doub
         if (t.kind[d] == PEM_DIST_UNIFORM) {
             v = (x >= a && x <= b) ? -log(b - a) : -__builtin_inf();
         } else if (t.kind[d] == PEM_DIST_LOGUNIFORM) {   // density of 10^U(a, b): 1 / (x ln10 (b - a))
-            v = (x >= pow(10.0, a) && x <= pow(10.0, b)) ? -log(x) - log(2.302585092994045684 * (b - a)) : -__builtin_inf();
+            v = (x >= t.lo[d] && x <= t.hi[d]) ? -log(x) - log(2.302585092994045684 * (b - a)) : -__builtin_inf();
         } else {
             const double z = (x - a) / b;
             v = -0.5 * z * z - log(b * 2.5066282746310002);
@@ -225,7 +227,7 @@ extern "C" int pem_loglik_marginal_f64_dev(size_t n_chains, int n_draws, int n_c
 }
 
 extern "C" int pem_log_prior_f64_dev(size_t n, int ndim, const int32_t* kind, const double* a, const double* b,
-                                     const double* theta, double* out, pem_stream_t stream) {
+                                     const double* lo, const double* hi, const double* theta, double* out, pem_stream_t stream) {
     if (ndim < 1 || ndim > PEM_SAMPLE_MAX_DIM) return pem::fail(PEM_ERR_INVALID_ARG, "pem_log_prior: 1 <= ndim <= %d", PEM_SAMPLE_MAX_DIM);
     if (!kind || !a || !b) return pem::fail(PEM_ERR_INVALID_ARG, "pem_log_prior: NULL prior table");
     PriorTable t{};
@@ -234,6 +236,8 @@ extern "C" int pem_log_prior_f64_dev(size_t n, int ndim, const int32_t* kind, co
         t.kind[d] = kind[d];
         t.a[d] = a[d];
         t.b[d] = b[d];
+        t.lo[d] = lo ? lo[d] : pow(10.0, a[d]);
+        t.hi[d] = hi ? hi[d] : pow(10.0, b[d]);
     }
     if (n == 0) return PEM_OK;
     if (!theta || !out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_log_prior: NULL array");

@@ -307,9 +307,12 @@ int pem_loglik_marginal_f64_dev(size_t n_chains, int n_draws, int n_cond, const 
                                 const double* a_1, double discharge_current, double discharge_sigma,
                                 const double* log_prior, double* out, pem_stream_t stream);
 /* out[i] = sum_d log pdf_d(theta[i][d]) for the PEM_DIST_* table (kind, a, b: host arrays, ndim <= 32); -inf outside
- * the support of a uniform / log-uniform variable.                                                                 */
-int pem_log_prior_f64_dev(size_t n, int ndim, const int32_t* kind, const double* a, const double* b,
-                          const double* theta, double* out, pem_stream_t stream);
+ * the support of a uniform / log-uniform variable.  lo, hi (host arrays or NULL): the support [lo, hi] of each log-uniform
+ * entry, ignored for the other kinds.  A caller that also decides the support itself passes the 10^a, 10^b it compares
+ * against (calibration.BatchedPosterior passes log_prior's 10.0 ** a), so that both decisions are the same bit for bit;
+ * NULL takes the host C library's pow(10, a), pow(10, b), which need not round as the caller's own code does.      */
+int pem_log_prior_f64_dev(size_t n, int ndim, const int32_t* kind, const double* a, const double* b, const double* lo,
+                          const double* hi, const double* theta, double* out, pem_stream_t stream);
 
 /* ---- SVD compression / reconstruction of field QoIs (fp64 MFMA) --------------------------------
  * Stand in for amisc `Compression(method='svd')` on `j_ion` (norm log10) and `u_ion` (norm linear(1e-3)):
