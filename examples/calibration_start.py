@@ -5,7 +5,8 @@
   2. the maximum a posteriori point by differential evolution over the prior's quantiles (optimize.DifferentialEvolution:
      the whole population is the rows of one posterior launch with shared nuisance draws, a generation is one graph replay);
   3. the Laplace approximation there (optimize.Laplace: a 2 d^2 + 1 point central-difference Hessian in one launch);
-  4. DRAM started from Laplace.dram_start().
+  4. DRAM started from Laplace.dram_start();
+  5. the chains' diagnostics (diagnostics.summary: split R-hat, ESS and MCSE beside the posterior's percentiles).
 
     python examples/calibration_start.py [n_steps]          (default 300 DRAM steps of 16 chains)
 """
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from hallthrusterpem_amd import diagnostics                                           # noqa: E402
 from hallthrusterpem_amd.calibration import DRAM, SystemPosterior                      # noqa: E402
 from hallthrusterpem_amd.likelihood import SystemLikelihood                            # noqa: E402
 from hallthrusterpem_amd.optimize import DifferentialEvolution, Laplace, stencil_size  # noqa: E402
@@ -85,4 +87,10 @@ torch.cuda.synchronize()
 print(f'DRAM: {n_steps} steps x {K} chains in {time.perf_counter() - t0:.1f} s, stage-1 acceptance '
       f'{float(sampler.acceptance[0].mean()):.2f}; posterior mean '
       f'{trace[n_steps // 10:].reshape(-1, len(names)).mean(0).cpu().numpy()} (theta* = {star})')
+
+# 5. can the trace be trusted?  show_mcmc / journal_plots with split R-hat, ESS and MCSE (10 % burn-in)
+t0 = time.perf_counter()
+diag = diagnostics.summary(trace, names=names, burnin=0.1, acceptance=sampler.acceptance)
+print(f'diagnostics in {1e3 * (time.perf_counter() - t0):.1f} ms')
+print(diagnostics.format_summary(diag))
 print(f'total {time.perf_counter() - t_start:.1f} s')

@@ -21,6 +21,7 @@ SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of t
 SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI groups of pem_sobol_sweep_f64_dev
 DE_MAX_POP, DE_MAX_DIM = 1024, 16   # PEM_DE_MAX_POP / PEM_DE_MAX_DIM: population and dimensions of pem_de_step_f64_dev
 DE_BEST1BIN, DE_RAND1BIN = 0, 1     # PEM_DE_*: its strategies
+CHAIN_TIME_BLOCK = 4096             # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -101,6 +102,7 @@ SIGNATURES = {
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),
+    'pem_chain_autocov_f64_dev': (C.c_int, [_sz, _sz, _sz, _dp] + [_sz] * 6 + [_dp, _dp, _dp, _sz, _dp]),
 }
 
 

@@ -611,6 +611,24 @@ int pem_de_step_f64_dev(int pop, int ndim, int strategy, int finalize, uint64_t 
                         double* pop_f, double* trial_u, const double* trial_f, double* theta, uint64_t* state, double* record,
                         double* history, size_t history_len, pem_stream_t stream);
 
+/* ---- MCMC chain diagnostics (hallthrusterpem_amd/diagnostics.py; the lag sums of uq.autocorrelation at
+ * scripts/pem_v0/mcmc.py:310 -- uqtils, third-party, parity UNPINNED).  x: fp64 [n_rows][ld], unit column stride (a
+ * (n, K, d) trace seen as n rows of K*d series; the pointer needs only 8-byte alignment).  Segment s is rows
+ * s*seg_stride ... s*seg_stride + seg_len - 1 (whole chains: n_seg 1; split halves: n_seg 2, seg_len floor(n/2),
+ * seg_stride ceil(n/2)).  With N = seg_len and y_t = x_t - mean, for i < n_lags, l = lag0 + i*lag_step:
+ *   mean[s][c]    = (1/N) sum_{t<N} x_t
+ *   acov[s][i][c] = (1/N) sum_{t<N-l} y_t y_{t+l}        (values centred as they are staged, before the products)
+ * A non-finite value makes that series' mean and every acov NaN in that segment; other series are untouched.  The sums
+ * run in an order that depends on N and the series only: the same bits on every run and whichever other lags the call
+ * asks for.  work: DEVICE scratch of work_len >= n_seg * ceil(seg_len / PEM_CHAIN_TIME_BLOCK) * n_lags * n_series
+ * doubles (one partial per time block).  Refused with PEM_ERR_INVALID_ARG: a zero size, ld < n_series, seg_len < 2, a
+ * segment past n_rows, a lag >= seg_len, lag_step 0, a null pointer, a short workspace.  lag_step > 1 costs what the
+ * lags lag0 ... lag0 + (n_lags - 1) lag_step cost, less the 128-lag blocks that hold no requested lag.              */
+#define PEM_CHAIN_TIME_BLOCK 4096
+int pem_chain_autocov_f64_dev(size_t n_rows, size_t n_series, size_t ld, const double* x, size_t n_seg, size_t seg_len,
+                              size_t seg_stride, size_t lag0, size_t lag_step, size_t n_lags, double* mean, double* acov,
+                              double* work, size_t work_len, pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
