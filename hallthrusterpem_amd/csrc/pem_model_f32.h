@@ -21,7 +21,8 @@ constexpr int NQ = 3;                         // V_cc, div_angle, T_c
 constexpr float F_PI = 3.14159265358979323846f;
 constexpr float F_HALF_PI = 1.57079632679489661923f;
 constexpr float F_GRID_H = 1.57079632679489661923f / 90.0f;
-constexpr float F_ALPHA_OVERFLOW = 53.28349511409265f;   // |a| beyond which the reference's erfi bracket is NaN
+constexpr float F_ALPHA_OVERFLOW = 53.28349511409265f;   // |a| beyond which the reference's erfi bracket is NaN.  The float is the
+                                                         // first one ABOVE the bound: |a| < it is |a| <= 53.28349511409265 exactly
 constexpr int ROW = 8;                        // D rows padded to 8 floats, Q rows to 8 float2: 16-byte LDS reads
 constexpr int NQROWS = PEM32_NDI + PEM32_NQB;
 constexpr int LDS_FLOATS = PEM32_NDI * ROW + NQROWS * ROW * 2 + 2 * 96;
@@ -73,7 +74,7 @@ __device__ __forceinline__ float normaliser32(float a, float u, const float* dpo
 #pragma unroll
     for (int j = PEM32_NDAW - 2; j >= 0; --j) s = fmaf(s, y, PEM32_DAWSON[j]);
     float D = (fabsf(a) < 0.25f) ? F_PI * a2 * s : d;
-    if (!(fabsf(a) <= F_ALPHA_OVERFLOW) || a == 0.0f) D = __builtin_nanf("");
+    if (!(fabsf(a) < F_ALPHA_OVERFLOW) || a == 0.0f) D = __builtin_nanf("");
     return D;
 }
 
