@@ -22,6 +22,9 @@ SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI gr
 DE_MAX_POP, DE_MAX_DIM = 1024, 16   # PEM_DE_MAX_POP / PEM_DE_MAX_DIM: population and dimensions of pem_de_step_f64_dev
 DE_BEST1BIN, DE_RAND1BIN = 0, 1     # PEM_DE_*: its strategies
 CHAIN_TIME_BLOCK = 4096             # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
+MARGINALS_MAX_PAR, MARGINALS_MAX_BINS = 32, 64   # PEM_MARGINALS_MAX_PAR / _MAX_BINS: parameters and bins of pem_chain_hist_f64_dev
+HIST_ROW_TILE = 128                 # PEM_HIST_ROW_TILE: rows it bins per stage
+KDE_MAX_GRID, KDE_ROW_BLOCK = 4096, 4096   # PEM_KDE_MAX_GRID / PEM_KDE_ROW_BLOCK: grid points and rows per workspace partial of pem_chain_kde_f64_dev
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -103,6 +106,8 @@ SIGNATURES = {
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),
     'pem_chain_autocov_f64_dev': (C.c_int, [_sz, _sz, _sz, _dp] + [_sz] * 6 + [_dp, _dp, _dp, _sz, _dp]),
+    'pem_chain_hist_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, C.c_int, _dp] + [_dp] * 4 + [_dp]),
+    'pem_chain_kde_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, _sz, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
 }
 
 

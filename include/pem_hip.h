@@ -629,6 +629,44 @@ int pem_chain_autocov_f64_dev(size_t n_rows, size_t n_series, size_t ld, const d
                               size_t seg_stride, size_t lag0, size_t lag_step, size_t n_lags, double* mean, double* acov,
                               double* work, size_t work_len, pem_stream_t stream);
 
+/* ---- marginals of a pooled MCMC trace (csrc/pem_marginals.hip, hallthrusterpem_amd/marginals.py; the arrays behind
+ * uq.ndscatter at scripts/pem_v0/mcmc.py:339-385 -- uqtils, third-party, parity UNPINNED; the definitions are numpy's
+ * np.histogram / np.histogram2d with range= given and scipy.stats.gaussian_kde's formula).  x: fp64 [n_rows][ld], unit
+ * column stride, n_par <= ld columns used, read in place (8-byte alignment suffices).  Every array is a DEVICE array.
+ *
+ * pem_chain_hist_f64_dev: edges [n_par][bins + 1], non-decreasing per parameter (the caller's np.linspace).  A value v of
+ * parameter i is in bin k iff edges[i][k] <= v < edges[i][k+1], the last bin also taking v == edges[i][bins]; anything else
+ * (outside, NaN, +-inf) is in no bin.  The decision is a comparison against the table.
+ *   hist1d[i][k]          draws with parameter i in bin k
+ *   hist2d[p][ki][kj]     pair p = (i, j), i < j, in the order (0,1), (0,2) ... (n_par-2, n_par-1): draws with parameter i in
+ *                         bin ki AND parameter j in bin kj; NULL: 1-D only
+ *   dropped[i]            draws of parameter i in no bin;  nonfinite[i]: how many of those were NaN or +-inf
+ * Exact 64-bit counts (integer adds: the same for every run).  The outputs are zeroed by the call.
+ *
+ * pem_chain_kde_f64_dev: grid [n_par][n_grid], inv_h [n_par] (1 / bandwidth), scale [n_par] (inv_h / (n_rows sqrt(2 pi))):
+ *   kde[i][q] = scale[i] * sum_t exp(-((grid[i][q] - x[t][i]) * inv_h[i])^2 / 2)
+ * a direct, untruncated sum; the difference grid - x is formed first.  Each wave sums its rows of a PEM_KDE_ROW_BLOCK-row
+ * block in increasing t, the 4 wave sums are added in order, one partial per row block goes to work (work_len >=
+ * ceil(n_rows / PEM_KDE_ROW_BLOCK) * n_par * n_grid doubles) and the partials are added in block order: the same bits on
+ * every run, and a grid point's value does not depend on the other grid points.  A NaN inv_h gives NaN for that parameter.
+ *
+ * Refused with PEM_ERR_INVALID_ARG: a zero size, n_par outside 1 ... PEM_MARGINALS_MAX_PAR, bins outside 1 ...
+ * PEM_MARGINALS_MAX_BINS, n_grid > PEM_KDE_MAX_GRID, ld < n_par, a null pointer (hist2d excepted), a short workspace,
+ * n_rows beyond one launch.  For the counts: a workgroup's 32-bit tables must see fewer than 2^32 rows, and the launch
+ * has floor(1024 / task blocks) row blocks (at most; task blocks = ceil(tables / min(256, floor(9216 / bins^2))), tables = n_par or
+ * n_par (n_par + 1) / 2), so n_rows >= 2^32 * floor(1024 / task blocks) is refused: 2^42 with one task block, 2^40 at
+ * n_par = 17, bins = 15.  For the density: more than 65535 row blocks, n_rows > 65535 * PEM_KDE_ROW_BLOCK.              */
+#define PEM_MARGINALS_MAX_PAR 32
+#define PEM_MARGINALS_MAX_BINS 64
+#define PEM_HIST_ROW_TILE 128
+#define PEM_KDE_MAX_GRID 4096
+#define PEM_KDE_ROW_BLOCK 4096
+int pem_chain_hist_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, int bins, const double* edges,
+                           uint64_t* hist1d, uint64_t* hist2d, uint64_t* dropped, uint64_t* nonfinite, pem_stream_t stream);
+int pem_chain_kde_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, size_t n_grid, const double* grid,
+                          const double* inv_h, const double* scale, double* kde, double* work, size_t work_len,
+                          pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
