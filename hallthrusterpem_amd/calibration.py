@@ -22,6 +22,10 @@ its `c1` is the anomalous-transport coefficient, PEM variable `a_1`).
 `SystemPosterior` is the same flow for the reference's `System` calibration (mcmc.py:28-45, QOIS = V_cc, T, uion, jion): each
 quantity from its own dataset at its own operating conditions (`likelihood.SystemLikelihood`), all compared in ONE fused launch
 (`pem_coupled_system_loglik_f64_dev`), so that the cathode parameters are constrained by data as well as the plume's.
+
+`SurrogatePosterior` is that flow as the reference runs it: the trained component surrogates (`chain.ChainedSurrogate`) in the
+model's place, j_ion rebuilt from its SVD latents and I_D taken from the surrogate's output, all in ONE launch
+(`pem_chain_system_loglik_f64_dev`) -- what a plugged-in thruster solver that costs seconds per sample needs.
 """
 import ctypes as C
 import math
@@ -232,6 +236,137 @@ class SystemPosterior(BatchedPosterior):
 
     def _run_loglik(self):
         self.batch.run_system_loglik(self.lik, out=self.loglik)
+
+
+class SurrogateInputMap:
+    """Which rows of the (15, n) physical inputs a chained surrogate reads and how they become its normalised coordinates; which
+    rows it holds fixed.  Built and checked on the host (`surrogate_input_map`); `coords` is the numpy form of the map."""
+
+    def __init__(self, rows, is_log, a, b, fixed_rows, fixed_vals):
+        self.rows = np.asarray(rows, dtype=np.int64)                 # COUPLED_INPUTS rows of the surrogate's varied inputs, in its order
+        self.is_log = np.asarray(is_log, dtype=bool)
+        self.a, self.b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        self.fixed_rows = np.asarray(fixed_rows, dtype=np.int64)
+        self.fixed_vals = np.asarray(fixed_vals, dtype=np.float64)
+
+    def coords(self, x):
+        """x: (15, n) physical inputs -> (n_ext, n) coordinates, the expression of `PemV0System._external_coords`: log10 for
+        the log-uniform variables, then 2.0 * (u - a) / (b - a) - 1.0 left to right"""
+        x = np.asarray(x, dtype=np.float64)
+        t = np.empty((len(self.rows), x.shape[1]))
+        for d, r in enumerate(self.rows):
+            u = np.log10(x[r]) if self.is_log[d] else x[r]
+            t[d] = 2.0 * (u - self.a[d]) / (self.b[d] - self.a[d]) - 1.0
+        return t
+
+
+def surrogate_input_map(theta_names, operating, varied, fixed, priors, qois=(), field: bool = True):
+    """The input map of a posterior evaluated through a chained surrogate (`chain.ChainedSurrogate`: its `varied`, `fixed`,
+    `priors`, whether it carries the j_ion latents) for the calibrated `theta_names`, the (Ne, 3) `operating` rows of P_b, V_a,
+    mdot_a and the measured `qois`.  Runs without a device.  ValueError for what the surrogate cannot serve."""
+    varied, fixed = tuple(varied), dict(fixed)
+    for k in theta_names:
+        if k in fixed:
+            raise ValueError(f"'{k}' cannot be calibrated: the surrogate holds it fixed at {fixed[k]}")
+        if k not in varied:
+            raise ValueError(f"'{k}' cannot be calibrated: the surrogate does not know it (its varied inputs are {varied})")
+    if 'uion' in qois:
+        raise ValueError("the likelihood holds 'uion' records: the chain carries no u_ion latents yet (the thruster stage predicts "
+                         "I_B0 and T only)")
+    if 'jion' in qois and not field:
+        raise ValueError("the likelihood holds 'jion' records and the surrogate was built with field=False: it carries no j_ion latents")
+    op = np.atleast_2d(np.asarray(operating, dtype=np.float64))
+    for j, k in enumerate(OPERATING):
+        v = op[:, j]
+        if k in fixed:
+            if not np.all(v == fixed[k]):
+                raise ValueError(f"the surrogate holds the operating input '{k}' fixed at {fixed[k]}; conditions ask for "
+                                 f"{v[v != fixed[k]]}")
+        elif k in varied:
+            p = priors[k]
+            if p.kind == NORMAL:
+                raise ValueError(f"'{k}': a surrogate's box is uniform or log-uniform")
+            with np.errstate(divide='ignore', invalid='ignore'):
+                u = np.log10(v) if p.kind == LOGUNIFORM else v
+            out = ~((u >= p.a) & (u <= p.b))
+            if out.any():
+                lo, hi = (10.0 ** p.a, 10.0 ** p.b) if p.kind == LOGUNIFORM else (p.a, p.b)
+                raise ValueError(f"operating values of '{k}' outside the surrogate's box [{lo}, {hi}]: {v[out]}")
+        else:
+            raise ValueError(f"the surrogate neither varies nor fixes the operating input '{k}'")
+    for k in varied:
+        if priors[k].kind == NORMAL:
+            raise ValueError(f"'{k}': a surrogate's box is uniform or log-uniform")
+    fx = [k for k in COUPLED_INPUTS if k in fixed]
+    return SurrogateInputMap([COUPLED_INPUTS.index(k) for k in varied], [priors[k].kind == LOGUNIFORM for k in varied],
+                             [priors[k].a for k in varied], [priors[k].b for k in varied],
+                             [COUPLED_INPUTS.index(k) for k in fx], [float(fixed[k]) for k in fx])
+
+
+class SurrogatePosterior(BatchedPosterior):
+    def __init__(self, theta_names, likelihood: SystemLikelihood, surrogate, n_chains: int, n_nuisance: int = 100, seed: int = 0,
+                 discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False):
+        """`SystemPosterior` with a trained `chain.ChainedSurrogate` in the model's place, as the reference calibrates
+        (mcmc.py:57-106: `SURR.predict`, `jion_reconstruct`, I_D from the surrogate's output).  The interface of
+        `SystemPosterior`.  The priors are the surrogate's (its coordinates are defined over them); inputs it holds fixed are
+        written as constants; every other varied input that is neither calibrated nor operating is a nuisance draw.  One
+        evaluation: the physical inputs assembled as in `BatchedPosterior`, the surrogate's rows mapped to coordinates on the
+        device, ONE `pem_chain_system_loglik_f64_dev` (chain, j_ion nodes, Gaussian sums and the discharge term from the
+        surrogate's I_B0), then `pem_loglik_marginal_f64_dev` without a discharge term of its own.  `likelihood` may hold V_cc, T
+        and jion records; uion is refused (`surrogate_input_map`)."""
+        import torch
+        if not likelihood.use_discharge:
+            discharge = None
+        self.surrogate = surrogate
+        self.map = surrogate_input_map(theta_names, likelihood.operating, surrogate.varied, surrogate.fixed, surrogate.priors,
+                                       likelihood.qois, field=surrogate.field is not None)
+        if likelihood.device != surrogate.device:
+            raise ValueError(f'the likelihood lives on {likelihood.device}, the surrogate on {surrogate.device}')
+        self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, surrogate.priors, seed, None,
+                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance)
+        self.chain_discharge = None if discharge is None else (float(discharge[0]), float(discharge[1]))   # added by the launch
+        dev = lambda a, **kw: torch.as_tensor(a, device=self.device, **kw)                                   # noqa: E731
+        m = self.map
+        self._lin_src, self._log_src = dev(m.rows[~m.is_log]), dev(m.rows[m.is_log])
+        self._lin_dst, self._log_dst = dev(np.nonzero(~m.is_log)[0]), dev(np.nonzero(m.is_log)[0])
+        self._ca, self._cw = dev(m.a)[:, None], dev(m.b)[:, None] - dev(m.a)[:, None]        # the width divides as a device tensor
+        self._fixed_idx = dev(m.fixed_rows)
+        self._fixed_vals = dev(m.fixed_vals)[:, None]
+        self._u = torch.empty((len(m.rows), self.n), dtype=torch.float64, device=self.device)
+        self.coords = torch.empty_like(self._u)                                                # the last evaluation's coordinates
+        self._a1_row = COUPLED_INPUTS.index('a_1')
+
+    def assemble_inputs(self, theta):
+        """`BatchedPosterior.assemble_inputs`, then the inputs the surrogate holds fixed as constants, then its coordinates:
+        log10 for the log-uniform rows and 2.0 * (u - a) / (b - a) - 1.0 left to right (`PemV0System._external_coords`)"""
+        import torch
+        super().assemble_inputs(theta)
+        x = self.batch.inputs
+        if self._fixed_idx.numel():
+            x.index_copy_(0, self._fixed_idx, self._fixed_vals.expand(-1, self.n))
+        if self._lin_src.numel():
+            self._u.index_copy_(0, self._lin_dst, x.index_select(0, self._lin_src))
+        if self._log_src.numel():
+            self._u.index_copy_(0, self._log_dst, torch.log10(x.index_select(0, self._log_src)))
+        torch.sub(2.0 * (self._u - self._ca) / self._cw, 1.0, out=self.coords)
+
+    def _run_loglik(self, pred=None):
+        d = self.chain_discharge
+        self.surrogate.run_system_loglik(self.coords, self.lik, a_1=self.batch.inputs[self._a1_row] if d else None, discharge=d,
+                                         out=self.loglik, pred=pred)
+
+    def record_predictions(self, theta):
+        """(K M, n_rec) model values of the surrogate at every record of the table for theta (K, n_theta): row k M + m holds
+        draw m of chain k, conditions side by side as in `SystemLikelihood.rec`; padding records are NaN.  The nuisance draws
+        are those of the next evaluation and are not used up."""
+        import torch
+        assert theta.shape == (self.K, len(self.names)) and theta.dtype == torch.float64 and theta.device == self.device
+        pred = torch.full((self.K * self.M, self.lik.n_rec), math.nan, dtype=torch.float64, device=self.device)
+        fresh, self.fresh = self.fresh, False
+        self.assemble_inputs(theta)
+        self.fresh = fresh
+        self._run_loglik(pred=pred)
+        return pred
 
 
 def capture_graph(body, device, warmup: int = 2, generator=None):

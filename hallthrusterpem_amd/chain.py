@@ -240,6 +240,60 @@ class ChainedSurrogate:
                 c.scale if rebuild else 1.0, p(basis), p(fld), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return out, fld
 
+    def run_system_loglik(self, t, likelihood, a_1=None, discharge=None, out=None, pred=None, qoi=None):
+        """The chain and the multi-QoI log-likelihood of a `likelihood.SystemLikelihood` in ONE launch
+        (`pem_chain_system_loglik_f64_dev`): the surrogate in the model's place, as the reference calibrates (mcmc.py:57-106).
+        t: [n_ext][n] normalised external coordinates (unit column stride); sample i belongs to condition i mod n_cond.
+        a_1, discharge: the (n,) anomalous-transport inputs and (I_d, sigma): the discharge-current term with I_d = I_B0 /
+        (1 - 2 a_1) from the surrogate's I_B0 is added to every sample (both or neither).
+        out: the (n,) per-sample sums (allocated when None; returned).  pred: a (ceil(n / n_cond), >= n_rec) tensor that receives
+        the model value of every record.  qoi: a (4 + plume outputs, >= n) tensor that receives the rows of `predict`.
+        The j_ion map (norm, scale, rank, basis) is this chain's compression; without one (`field=False`) j_ion records give NaN."""
+        import torch
+        lk = likelihood
+        st, _keep = self.stage_tables()
+
+        def f64(x, what):
+            if x.dtype != torch.float64 or x.device != self.device:
+                raise ValueError(f'{what} must be a float64 tensor on {self.device}')
+            return True
+        f64(t, 't')
+        if t.dim() != 2 or t.shape[0] != self.n_ext or (t.shape[0] and t.stride(1) != 1):
+            raise ValueError(f't must be [{self.n_ext}][n] with unit column stride, got {tuple(t.shape)}')
+        n = t.shape[1]
+        if (a_1 is None) != (discharge is None):
+            raise ValueError('the discharge term needs both a_1 and discharge = (I_d, sigma)')
+        if a_1 is not None:
+            f64(a_1, 'a_1')
+            if a_1.shape != (n,) or not a_1.is_contiguous():
+                raise ValueError(f'a_1 must be a contiguous ({n},) tensor')
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=self.device)
+        f64(out, 'out')
+        if out.shape != (n,) or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous ({n},) tensor')
+        rows = -(-n // lk.n_cond)
+        if pred is not None and (f64(pred, 'pred') and (pred.dim() != 2 or pred.stride(1) != 1 or pred.shape[0] < rows
+                                                        or pred.shape[1] < lk.n_rec)):
+            raise ValueError(f'pred must be a ({rows}, >= {lk.n_rec}) tensor with unit column stride')
+        n_plume = self.stages[2].n_out
+        if qoi is not None and (f64(qoi, 'qoi') and (qoi.dim() != 2 or qoi.stride(1) != 1 or qoi.shape[0] < 4 + n_plume
+                                                     or qoi.shape[1] < n)):
+            raise ValueError(f'qoi must be a ({4 + n_plume}, >= {n}) tensor with unit column stride')
+        c = self.compression if self.field else None
+        basis = c.basis.contiguous() if c is not None else None
+        (vlo, vhi), (ilo, ihi) = self.domains
+        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None                                 # noqa: E731
+        d = discharge if discharge is not None else (0.0, 1.0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_chain_system_loglik_f64_dev(
+                n, self.n_dim, self.vcc_slot, self.ib0_slot, st, vlo, vhi - vlo, ilo, ihi - ilo, p(t), max(t.stride(0), n) if self.n_ext else n,
+                1, c.rank if c is not None else 0, FIELDS['j_ion'], c.norm if c is not None else 0, c.scale if c is not None else 1.0,
+                p(basis), lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), p(a_1), float(d[0]), float(d[1]), p(out),
+                p(qoi), qoi.stride(0) if qoi is not None else 0, p(pred), pred.stride(0) if pred is not None else 0,
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        return out
+
     def predict_fields(self, t):
         """t: [n_ext][n] -> {V_cc, I_B0, T, div_angle, T_c: (n,)[, j_ion: (n, 91), j_ion_latent: (n, rank)]}"""
         out, fld = self.predict(t)

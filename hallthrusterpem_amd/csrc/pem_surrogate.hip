@@ -436,6 +436,165 @@ void launch_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const ChainSt
                        ib0_slot, s[0], s[1], s[2], map[0], map[1], map[2], map[3], t, ld, out, ld_out, basis_words, rc);
 }
 
+// ---- the chain fused with the multi-QoI likelihood: the surrogate in the model's place inside the calibration --------------------
+// scripts/pem_v0/mcmc.py:57-106: `SURR.predict`, `jion_reconstruct`, the Gaussian sums, I_D from the surrogate's own output.  The
+// stages are sparse_chain_kernel's (stage_predict, coupling_coord: the same bits); the epilogue is one lane per sample, as
+// system_epilogue_sum of the coupled kernel: the j_ion nodes its condition's records touch are rebuilt from the latents (rebuild_field's
+// expression) and compared at once, so that the 91-point profile exists nowhere.
+struct ChainLik {
+    const double* basis;     // [91][rank] or NULL: no j_ion
+    const double* rec;       // [n_rec][4] {w, y, 1/std, bits}
+    const int32_t* span;     // [n_cond][4 kinds][2] {first record, count}
+    const double* a_1;       // NULL or [n]: the discharge-current term
+    double* loglik;          // [n]
+    double* out;             // NULL or the chain's rows
+    double* pred;            // NULL or [ceil(n / n_cond)][ld_pred]
+    size_t ld_out, ld_pred;
+    int lat0, rank, norm, n_cond, n_rec, staged;
+    double scale, discharge, inv_sigma;
+};
+
+// profile node k from this thread's latents (`lat`: its LDS slots, latent q at q * BLOCK): rebuild_field's sum and denormalisation
+__device__ __forceinline__ double jion_node(const double* lat, const double* jb, int k, int rank, int norm, double scale) {
+    double v = 0.0;
+    for (int q = 0; q < rank; ++q) v = fma(lat[q * BLOCK], jb[k * rank + q], v);
+    if (norm == PEM_NORM_LOG10) v = exp10(v);
+    else if (norm == PEM_NORM_LINEAR) v = v / scale;
+    return v;
+}
+
+// The records of sample i (condition i mod n_cond) against the chain's values: the sum in the order j_ion, V_cc, T, then the
+// discharge term; `store`: this lane's sample exists (a dead lane recomputes the last one and writes nothing).  Adjacent lanes belong
+// to different conditions: the loops diverge and every lane reads its own records (the odd padding of the blocks spreads them over
+// the banks).  Consecutive j_ion records mostly share a node or sit on neighbouring intervals: a node value depends on k alone, so
+// the last two are kept.
+__device__ __forceinline__ void chain_loglik_epilogue(const ChainLik& lk, const double* rec, const int32_t* span, const double* jb,
+                                                      const double* lat, long long i, bool store, double V_cc, double I_B0, double T) {
+#pragma clang fp contract(off)
+    const long long d = i / lk.n_cond;
+    const int c = (int)(i - d * lk.n_cond);
+    const double4* r4 = reinterpret_cast<const double4*>(rec);
+    const int2* sp = reinterpret_cast<const int2*>(span) + 4 * c;
+    const int2 rj = sp[PEM_SYS_JION], rv = sp[PEM_SYS_VCC], rt = sp[PEM_SYS_T], ru = sp[PEM_SYS_UION];
+    double* prow = (lk.pred && store) ? lk.pred + (size_t)d * lk.ld_pred : nullptr;
+    double ll = 0.0;
+    if (jb) {
+        int pk = -2;
+        double lo = 0.0, hi = 0.0;
+        for (int r = max(rj.x, 0); r < min(rj.x + rj.y, lk.n_rec); ++r) {
+            const double4 e = r4[r];
+            const int k = (int)min((unsigned)__double_as_longlong(e.w), 89u);
+            if (k == pk + 1) {
+                lo = hi;
+                hi = jion_node(lat, jb, k + 1, lk.rank, lk.norm, lk.scale);
+            } else if (k != pk) {
+                lo = jion_node(lat, jb, k, lk.rank, lk.norm, lk.scale);
+                hi = jion_node(lat, jb, k + 1, lk.rank, lk.norm, lk.scale);
+            }
+            pk = k;
+            const double m = fma(e.x, hi - lo, lo);
+            if (prow) prow[r] = m;
+            const double z = (e.y - m) * e.z;
+            ll = fma(-0.5 * z, z, ll);
+        }
+    }
+    for (int r = max(rv.x, 0); r < min(rv.x + rv.y, lk.n_rec); ++r) {   // the cathode stage's coupling voltage
+        const double4 e = r4[r];
+        if (prow) prow[r] = V_cc;
+        const double z = (e.y - V_cc) * e.z;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    for (int r = max(rt.x, 0); r < min(rt.x + rt.y, lk.n_rec); ++r) {   // the thruster stage's thrust T (not T_c)
+        const double4 e = r4[r];
+        if (prow) prow[r] = T;
+        const double z = (e.y - T) * e.z;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    // what the chain cannot give is made visible: no u_ion latents, or j_ion records without a basis
+    if (ru.y > 0 || (!jb && rj.y > 0)) ll = __builtin_nan("");
+    if (lk.a_1) {                                                       // I_d of the test double from the SURROGATE's I_B0 (mcmc.py:101)
+        const double den = 1.0 - 2.0 * lk.a_1[i];
+        const double i_d = I_B0 / den;
+        const double z = (lk.discharge - i_d) * lk.inv_sigma;
+        ll = fma(-0.5 * z, z, ll);
+    }
+    if (store) lk.loglik[i] = ll;
+}
+
+template <int NOUT, bool EXACT>
+__global__ __launch_bounds__(BLOCK) void chain_loglik_kernel(long long n, int n_dim, int vcc_slot, int ib0_slot, ChainStage cat, ChainStage thr,
+                                                             ChainStage plu, double vcc_lo, double vcc_w, double ib0_lo, double ib0_w,
+                                                             const double* __restrict__ t, size_t ld, int basis_words, ChainLik lk) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* basis = lds;                                    // every stage's outer bases in turn; later: this thread's latents [rank][BLOCK]
+    double* coord = lds + (size_t)basis_words * BLOCK;      // [n_dim][BLOCK]
+    const int n_out = EXACT ? NOUT : plu.n_out;
+    const int tid = threadIdx.x;
+    // the measurement table, the spans and the j_ion basis: beside the coordinates where the launch found room, else through the cache
+    const double* rec = lk.rec;
+    const int32_t* span = lk.span;
+    const double* jb = lk.basis;
+    if (lk.staged) {
+        double* srec = coord + (size_t)n_dim * BLOCK;
+        int32_t* sspan = reinterpret_cast<int32_t*>(srec + 4 * lk.n_rec);
+        double* sjb = srec + 4 * lk.n_rec + 4 * lk.n_cond;
+        for (int k = tid; k < 4 * lk.n_rec; k += BLOCK) srec[k] = lk.rec[k];
+        for (int k = tid; k < 8 * lk.n_cond; k += BLOCK) sspan[k] = lk.span[k];
+        if (lk.basis)
+            for (int k = tid; k < PEM_NANGLE * lk.rank; k += BLOCK) sjb[k] = lk.basis[k];
+        __syncthreads();
+        rec = srec;
+        span = sspan;
+        if (lk.basis) jb = sjb;
+    }
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long i0 = (long long)blockIdx.x * BLOCK; i0 < n; i0 += stride) {
+        const bool live = i0 + tid < n;
+        const long long i = live ? i0 + tid : n - 1;        // a dead lane recomputes the last point and stores nothing
+        for (int d = 0, r = 0; d < n_dim; ++d)
+            if (d != vcc_slot && d != ib0_slot) coord[d * BLOCK + tid] = t[(size_t)(r++) * ld + i];
+        // (each stage and the epilogue read and write this thread's own slots only: no barrier inside the loop)
+        double vcc[1], thrust[2], plume[NOUT];
+        stage_predict<1, true>(cat, coord, basis, tid, vcc);
+        coord[vcc_slot * BLOCK + tid] = coupling_coord(vcc[0], vcc_lo, vcc_w);
+        stage_predict<2, true>(thr, coord, basis, tid, thrust);
+        coord[ib0_slot * BLOCK + tid] = coupling_coord(thrust[0], ib0_lo, ib0_w);
+        stage_predict<NOUT, EXACT>(plu, coord, basis, tid, plume);
+        if (lk.out && live) {
+            double* out = lk.out;
+            const size_t ld_out = lk.ld_out;
+            out[i] = vcc[0];
+            out[ld_out + i] = thrust[0];
+            out[2 * ld_out + i] = thrust[1];
+            out[3 * ld_out + i] = plume[0];
+            out[4 * ld_out + i] = thrust[1] * cos(plume[0]);
+#pragma unroll
+            for (int o = 1; o < NOUT; ++o)
+                if (EXACT || o < n_out) out[(size_t)(4 + o) * ld_out + i] = plume[o];
+        }
+        // the latents leave the registers (the basis slots are free again): after this only V_cc, I_B0 and T are live
+        if (lk.basis) {
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o)
+                if (o >= lk.lat0 && o < lk.lat0 + lk.rank) basis[(o - lk.lat0) * BLOCK + tid] = plume[o];
+        }
+        chain_loglik_epilogue(lk, rec, span, jb, basis + tid, i, live, vcc[0], thrust[0], thrust[1]);
+    }
+}
+
+template <int NOUT, bool EXACT>
+void launch_chain_loglik(size_t n, int n_dim, int vcc_slot, int ib0_slot, const ChainStage (&s)[3], const double (&map)[4], const double* t,
+                         size_t ld, int basis_words, size_t lds, const ChainLik& lk, hipStream_t st) {
+    size_t blocks = (n + BLOCK - 1) / BLOCK;
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    if (lds > 64 * 1024) {
+        static pem::LdsAttrOnce attr;
+        (void)attr.ensure(reinterpret_cast<const void*>(chain_loglik_kernel<NOUT, EXACT>));      // a refusal shows as a launch error below
+    }
+    hipLaunchKernelGGL((chain_loglik_kernel<NOUT, EXACT>), dim3((unsigned)blocks), dim3(BLOCK), lds, st, (long long)n, n_dim, vcc_slot,
+                       ib0_slot, s[0], s[1], s[2], map[0], map[1], map[2], map[3], t, ld, basis_words, lk);
+}
+
 }  // namespace
 
 namespace {
@@ -477,10 +636,10 @@ int sparse_predict(const char* who, size_t n, int n_dim, int n_beta, const int32
     return PEM_OK;
 }
 
-int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
-                         double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out, const Recon& rc,
-                         pem_stream_t stream) {
-    const char* who = "pem_sparse_predict_chain";
+// what both chained entry points ask of the slots, the coupling domains and the three tables; fills the kernels' view of the stages
+// and the largest stage's outer-basis words per thread
+int check_chain(const char* who, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
+                double ib0_lo, double ib0_w, ChainStage (&cs)[3], int& basis_words) {
     if (!stages) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL stage array", who);
     if (n_dim < 2 || n_dim > PEM_SURR_MAX_DIM)
         return pem::fail(PEM_ERR_INVALID_ARG, "%s: 2 <= n_dim <= %d (the external coordinates and the two coupling slots)", who, PEM_SURR_MAX_DIM);
@@ -489,8 +648,7 @@ int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const 
     if (!std::isfinite(vcc_lo) || !std::isfinite(vcc_w) || !(vcc_w > 0.0) || !std::isfinite(ib0_lo) || !std::isfinite(ib0_w) || !(ib0_w > 0.0))
         return pem::fail(PEM_ERR_INVALID_ARG, "%s: a coupling domain needs a finite lo and a finite width w > 0", who);
     static const int need_out[3] = {1, 2, 0};          // cathode: V_cc; thruster: I_B0, T; plume: div_angle [, latents]
-    ChainStage cs[3];
-    int basis_words = 0;
+    basis_words = 0;
     for (int k = 0; k < 3; ++k) {
         const pem_surr_stage& g = stages[k];
         if (!g.index || !g.coef || !g.values) return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: NULL table", who, k);
@@ -504,6 +662,16 @@ int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const 
                            g.max_level == 0 ? 1 : (1 << g.max_level) + 1};
         if (cs[k].max_outer * cs[k].max_m > basis_words) basis_words = cs[k].max_outer * cs[k].max_m;
     }
+    return PEM_OK;
+}
+
+int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
+                         double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out, const Recon& rc,
+                         pem_stream_t stream) {
+    const char* who = "pem_sparse_predict_chain";
+    ChainStage cs[3];
+    int basis_words = 0;
+    if (int rc0 = check_chain(who, n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w, ib0_lo, ib0_w, cs, basis_words)) return rc0;
     const int n_plume = stages[2].n_out;
     if (rc.field && (rc.rank < 1 || rc.rank > 16 || rc.lat0 < 0 || rc.lat0 + rc.rank > n_plume || rc.dof < 1 || !rc.basis))
         return pem::fail(PEM_ERR_INVALID_ARG, "%s: the reconstructed field takes 1 <= rank <= 16 latent outputs lat0 .. lat0 + rank - 1 of the plume stage", who);
@@ -528,6 +696,58 @@ int sparse_predict_chain(size_t n, int n_dim, int vcc_slot, int ib0_slot, const 
             else PEM_CHAIN(16, false);
     }
 #undef PEM_CHAIN
+    HIP_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
+int chain_system_loglik(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
+                        double ib0_lo, double ib0_w, const double* t, size_t ld, int dof, double discharge_sigma, ChainLik lk,
+                        pem_stream_t stream) {
+    const char* who = "pem_chain_system_loglik";
+    ChainStage cs[3];
+    int basis_words = 0;
+    if (int rc0 = check_chain(who, n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w, ib0_lo, ib0_w, cs, basis_words)) return rc0;
+    const int n_plume = stages[2].n_out;
+    if (lk.basis) {
+        if (lk.rank < 1 || lk.rank > 16 || lk.lat0 < 0 || lk.lat0 + lk.rank > n_plume)
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: the j_ion map takes 1 <= rank <= 16 latent outputs lat0 .. lat0 + rank - 1 of the plume stage", who);
+        if (dof != PEM_NANGLE) return pem::fail(PEM_ERR_INVALID_ARG, "%s: the j_ion records index the %d-point profile: dof must be %d, got %d", who, PEM_NANGLE, PEM_NANGLE, dof);
+        if (lk.norm != PEM_NORM_NONE && lk.norm != PEM_NORM_LOG10 && lk.norm != PEM_NORM_LINEAR)
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: unknown norm %d", who, lk.norm);
+        if (lk.rank > basis_words) basis_words = lk.rank;          // the latents take the basis slots of their thread
+    }
+    const size_t base = (size_t)(basis_words + n_dim) * BLOCK * sizeof(double);
+    if (base > 160 * 1024)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the largest stage's outer bases and %d coordinates do not fit the LDS", who, n_dim);
+    if (lk.n_cond < 1 || lk.n_cond > PEM_FUSED_SYSTEM_MAX_RECORDS || lk.n_rec < 1 || lk.n_rec > PEM_FUSED_SYSTEM_MAX_RECORDS)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: 1 .. %d conditions and records (PEM_FUSED_SYSTEM_MAX_RECORDS)", who, PEM_FUSED_SYSTEM_MAX_RECORDS);
+    if (lk.a_1 && !(std::isfinite(discharge_sigma) && discharge_sigma > 0.0))
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the discharge term needs a finite discharge_sigma > 0", who);
+    if (n == 0) return PEM_OK;
+    if ((n_dim > 2 && !t) || !lk.rec || !lk.span || !lk.loglik) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL array", who);
+    if ((n_dim > 2 && ld < n) || (lk.out && lk.ld_out < n)) return pem::fail(PEM_ERR_INVALID_ARG, "%s: leading dimension smaller than n", who);
+    if (lk.pred && lk.ld_pred < (size_t)lk.n_rec) return pem::fail(PEM_ERR_INVALID_ARG, "%s: ld_pred smaller than n_rec", who);
+    if (int rc0 = pem::check_device()) return rc0;
+    lk.inv_sigma = lk.a_1 ? 1.0 / discharge_sigma : 0.0;
+    // the table, the spans and the basis go beside the coordinates where that costs no resident workgroup: the stages hold about
+    // 200 VGPRs, two workgroups per CU at most, so up to half of the 160 KB each; a launch that is alone on its CU anyway may fill it
+    const size_t extra = (size_t)lk.n_rec * 32 + (size_t)lk.n_cond * 32 + (lk.basis ? (size_t)PEM_NANGLE * lk.rank * sizeof(double) : 0);
+    const size_t room = base <= 80 * 1024 ? 80 * 1024 : 160 * 1024;
+    lk.staged = base + extra <= room;
+    const size_t lds = base + (lk.staged ? extra : 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const double map[4] = {vcc_lo, vcc_w, ib0_lo, ib0_w};
+#define PEM_CHAIN_LL(NOUT_, EXACT_) launch_chain_loglik<NOUT_, EXACT_>(n, n_dim, vcc_slot, ib0_slot, cs, map, t, ld, basis_words, lds, lk, st)
+    switch (n_plume) {
+        case 1: PEM_CHAIN_LL(1, true); break;
+        case 2: PEM_CHAIN_LL(2, true); break;
+        case 3: PEM_CHAIN_LL(3, true); break;
+        case 4: PEM_CHAIN_LL(4, true); break;
+        default:
+            if (n_plume <= 8) PEM_CHAIN_LL(8, false);
+            else PEM_CHAIN_LL(16, false);
+    }
+#undef PEM_CHAIN_LL
     HIP_TRY(hipGetLastError());
     return PEM_OK;
 }
@@ -585,6 +805,31 @@ int pem_sparse_predict_chain_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_
         rc.scale = norm_scale;
     }
     return sparse_predict_chain(n, n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w, ib0_lo, ib0_w, t, ld, out, ld_out, rc, stream);
+}
+
+int pem_chain_system_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                    double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, int lat0, int rank, int dof,
+                                    int norm, double norm_scale, const double* basis, int n_cond, int n_rec, const double* rec,
+                                    const int32_t* span, const double* a_1, double discharge_current, double discharge_sigma,
+                                    double* loglik, double* out, size_t ld_out, double* pred, size_t ld_pred, pem_stream_t stream) {
+    ChainLik lk{};
+    lk.basis = basis;
+    lk.rec = rec;
+    lk.span = span;
+    lk.a_1 = a_1;
+    lk.loglik = loglik;
+    lk.out = out;
+    lk.pred = pred;
+    lk.ld_out = ld_out;
+    lk.ld_pred = ld_pred;
+    lk.lat0 = lat0;
+    lk.rank = basis ? rank : 0;
+    lk.norm = norm;
+    lk.n_cond = n_cond;
+    lk.n_rec = n_rec;
+    lk.scale = norm_scale;
+    lk.discharge = discharge_current;
+    return chain_system_loglik(n, n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w, ib0_lo, ib0_w, t, ld, dof, discharge_sigma, lk, stream);
 }
 
 }  // extern "C"

@@ -386,6 +386,36 @@ int pem_sparse_predict_chain_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_
                                      double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out,
                                      int lat0, int rank, int dof, int norm, double norm_scale, const double* basis, double* field,
                                      pem_stream_t stream);
+/* The component chain and the Gaussian log-likelihood of several measured quantities in one launch: the surrogate in the place of the
+ * model inside the likelihood, as the reference calibrates (scripts/pem_v0/mcmc.py:57-106: `SURR.predict`, `jion_reconstruct`, the
+ * discharge current from the surrogate's own output; its surrogate is third-party: parity UNPINNED, held to the composition of
+ * pem_sparse_predict_chain_f64_dev and a long-double sum).  The chain arguments (n .. ld) as pem_sparse_predict_chain_f64_dev, and the
+ * chain's values equal that launch's bit for bit.  Sample i belongs to condition c = i mod n_cond; rec / span are
+ * pem_coupled_system_loglik_f64_dev's table (likelihood.SystemLikelihood), unchanged.  Per sample
+ *   j[k]          = denorm(v), v = 0; v = fma(p_{lat0+q}, basis[k][q], v), q = 0 .. rank - 1 (pem_sparse_predict_field_f64_dev's
+ *                   expression, dof == 91), at the nodes k, k + 1 of the condition's j_ion records only: no profile reaches HBM
+ *   PEM_SYS_JION    m = fma(w, j[k+1] - j[k], j[k])
+ *   PEM_SYS_VCC     m = V_cc
+ *   PEM_SYS_T       m = T, the thruster stage's second output (not T_c)
+ *   PEM_SYS_UION    the chain carries no u_ion latents: a condition with such records gets NaN, as does one with j_ion records when
+ *                   basis is NULL
+ *   loglik[i]     = sum -0.5 z^2, z = (y - m) * inv_std, one lane per sample, in the order j_ion, V_cc, T (each kind in record
+ *                   order), every term added by one fma(-0.5 z, z, sum)
+ *   a_1 (NULL or [n]): loglik[i] = fma(-0.5 z, z, loglik[i]) once more, z = (discharge_current - I_d) * (1 / discharge_sigma),
+ *                   I_d = I_B0 / (1 - 2 a_1[i]) with the SURROGATE's I_B0 (mcmc.py:101 takes I_D from the surrogate's output);
+ *                   marginalise with pem_loglik_marginal_f64_dev WITHOUT its own discharge term
+ * out (NULL or [4 + n_out(plume)][ld_out]): the rows of pem_sparse_predict_chain_f64_dev.  pred (NULL or [ceil(n / n_cond)][ld_pred],
+ * ld_pred >= n_rec): as pem_coupled_system_predict_f64_dev, sample i = d n_cond + c writes m of record r of condition c to
+ * pred[d * ld_pred + r]; padding records are neither summed nor written.  A sample's loglik and pred bits depend on its coordinates,
+ * its condition and the tables only -- not on n, its position, the grid or which optional outputs are asked for.
+ * n_cond, n_rec in 1 .. PEM_FUSED_SYSTEM_MAX_RECORDS; rank <= 16.  LDS: the chain's (a latent slot per thread included), and the
+ * record table, the spans and the basis beside it where they fit the 160 KB, else they are read through the cache (same bits).
+ * Every argument is checked before the device is. */
+int pem_chain_system_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                    double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, int lat0, int rank, int dof,
+                                    int norm, double norm_scale, const double* basis, int n_cond, int n_rec, const double* rec,
+                                    const int32_t* span, const double* a_1, double discharge_current, double discharge_sigma,
+                                    double* loglik, double* out, size_t ld_out, double* pred, size_t ld_pred, pem_stream_t stream);
 
 /* ---- per-column order statistics over the sample axis -------------------------------------------------------------
  * The percentiles of scripts/gen_data.py:125-174 (`np.percentile(arr, 25 | 75, axis=0)`, NaN / interquartile-range masks) and
