@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 
 #include "pem_hip.h"
 
@@ -68,6 +69,24 @@ inline hipError_t device_cus(int* out) {
     return hipSuccess;
 }
 
+// Balanced rounds: a persistent wave takes tiles me, me + nwaves, ...; with the largest grid that fits, a 1.25e6-sample shard is
+// 9.54 tiles per wave -- ten rounds, the last one 54 % full and as long as a full one (a tile's duration is latency, not
+// bandwidth: tools/tail_probe.py).  The smallest grid with the same number of rounds fills every round instead.
+// Only where that costs little occupancy (>= 90 % of the slots stay in use): with two or three rounds the balanced grid is much
+// smaller than the full one and the kernel loses more to the missing parallelism than it gains at the tail (plume_radii_kernel,
+// 1e5 samples x 25 radii, 1.2 rounds: 560 us with the full grid, 655 us balanced; profiles/reconstruct_balanced_r02z.txt).
+// PEM_BALANCED_GRID=0 restores the full grid everywhere.
+inline size_t balanced_grid(size_t need, size_t cap) {
+    static const bool balanced = getenv("PEM_BALANCED_GRID") ? atoi(getenv("PEM_BALANCED_GRID")) != 0 : true;
+    if (need <= cap) return need;
+    if (!balanced || cap == 0) return cap;
+    const size_t rounds = (need + cap - 1) / cap;
+    const size_t g = (need + rounds - 1) / rounds;
+    return 10 * g >= 9 * cap ? g : cap;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 // XCD-aware block order.  Workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one): with tile = workgroup index
 // every XCD touches every eighth piece of a streamed array; through this bijective remap (cdna_hip_programming.md: "XCD swizzle
 // must be bijective") the workgroups that share an XCD walk one contiguous eighth instead, and each XCD's L2 hands the memory
@@ -96,4 +115,9 @@ __device__ __forceinline__ unsigned xcd_contiguous_block() {
         if (e_ != hipSuccess)                                                                           \
             return pem::fail(e_ == hipErrorNoDevice ? PEM_ERR_NO_DEVICE : PEM_ERR_HIP, "%s: %s", #expr, \
                              hipGetErrorString(e_));                                                    \
+    } while (0)
+
+#define PEM_TRY(expr)                     \
+    do {                                  \
+        if (int rc_ = (expr)) return rc_; \
     } while (0)

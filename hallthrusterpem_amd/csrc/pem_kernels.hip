@@ -1,4 +1,5 @@
-// pem_kernels.hip -- gfx950 (MI355X, CDNA4) kernels + C ABI of libpem_hip.so.
+// pem_kernels.hip -- the gfx950 (MI355X, CDNA4) kernel of the one-radius plume path, plume_r1_kernel, its launch planning and the
+// entry points of libpem_hip.so's C ABI that launch it.
 //
 // What is computed (reference file:line, upstream repository root):
 //   cathode stage    src/hallmd/models/cathode.py:24-38
@@ -30,66 +31,31 @@
 //   * The same tile loop carries the fused modes: Monte-Carlo inputs generated in the prelude (MC) and the likelihood of
 //     measured current densities (JMODE 3) consuming the profile on chip.  (The fused SVD compression is a lane-per-sample
 //     kernel of its own, csrc/pem_latent.hip.)
-//   Other kernels in this file: plume_rfew_kernel (2..8 sweep radii: this design generalised), plume_radii_kernel /
-//   plume_generic_kernel (more radii), cathode, thruster, u_ion profile and the post-run filters.  The per-sample scalar
-//   stages and tables are csrc/pem_model.h (shared with the lane-per-sample kernels, csrc/pem_saltelli.hip and csrc/pem_latent.hip).
+//   Elsewhere: plume_rfew_kernel (2..8 sweep radii: this design generalised), plume_rmid_kernel / plume_radii_kernel /
+//   plume_generic_kernel (more radii) in csrc/pem_radii.hip; cathode, thruster, u_ion profile and the post-run filters in
+//   csrc/pem_stages.hip; the host-pointer entry points in csrc/pem_host.hip; the host side of the fused campaign statistics in
+//   csrc/pem_campaign.hip.  What these share is csrc/pem_plume.h; the per-sample scalar stages and tables are csrc/pem_model.h
+//   (shared with the lane-per-sample kernels, csrc/pem_saltelli.hip and csrc/pem_latent.hip).
 //
 // This file is written for gfx950 only: 64-wide waves, 160 KiB LDS, no portability layer.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdarg>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <atomic>
-#include <functional>
-#include <future>
 #include <mutex>
-#include <string>
-#include <thread>
 #include <type_traits>
 
-#include "pem_common.h"
 #include "pem_math.h"
-#include "pem_hip.h"
 #include "pem_philox.h"
-#include "pem_qfused.h"
-
-#include "pem_model.h"
+#include "pem_plume.h"
 
 namespace {
 
+using namespace pem;
 using namespace pem_model;
-
-constexpr int BLOCK = 256;                     // elementwise kernels
-constexpr int WAVE = 64;
 
 // ---------------------------------------------------------------------------------------------
 // kernel arguments
 // ---------------------------------------------------------------------------------------------
-struct PlumeIO {
-    long long n;
-    double torr2pa;
-    double radius;  // R = 1 fast path
-    const double *P_b, *c0, *c1, *c2, *c3, *c4, *c5, *sigma, *I_B0, *T;
-    double *j_ion, *div, *Tc;
-    uint8_t* invalid;
-    float* j_ion_f32;  // mixed mode: the profile is computed in fp64 and stored as fp32
-    // fused likelihood mode (JMODE 3): measurement tables [n_cond][n_ang] and the per-sample result
-    const int32_t* m_kidx;
-    const double *m_wgt, *m_y, *m_inv_std;
-    double* loglik;
-    int n_cond, n_ang;
-    // Where sample g of an input array lives: ptr[(g / 64) * in_tile_stride + g % 64].  64 = plain SoA arrays (every entry
-    // point but one); 15 * 64 = the tile-interleaved layout of pem_coupled_tiled_f64_dev, whose 15 "arrays" are the rows of
-    // one [tiles][15][64] block (R = 1 fast path only: the other plume kernels index the arrays directly).
-    long long in_tile_stride = 64;
-    // counting modes (JMODE 4 / 5): brackets in, counts and records out (csrc/pem_qfused.h)
-    pem::CountIO q;
-};
-
 struct CoupledIO {
     const double *V_a, *T_e, *V_vac, *Pstar, *P_T, *mdot_a, *a_1;
     double *V_cc, *I_B0, *T;
@@ -134,46 +100,29 @@ struct SampleIn {
     double x0, x1, x2, x3, x4, x5, x6;  // COUPLED: V_a T_e V_vac Pstar P_T mdot_a a_1 ; else I_B0, T, unused
 };
 
-// read-once input stream
-__device__ __forceinline__ double stream_load(const double* p) {
-#if defined(PEM_NT_LOADS) && PEM_NT_LOADS
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-
-__device__ __forceinline__ void stream_store1(double v, double* p) {
-#if defined(PEM_NT_QOI) && PEM_NT_QOI
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-
 template <bool COUPLED>
 __device__ __forceinline__ SampleIn<COUPLED> load_sample(const PlumeIO& io, const CoupledIO& cio, long long gi) {
     SampleIn<COUPLED> v;
     gi = (gi >> 6) * io.in_tile_stride + (gi & 63);
-    v.P_b = stream_load(io.P_b + gi);
-    v.c0 = stream_load(io.c0 + gi);
-    v.c1 = stream_load(io.c1 + gi);
-    v.c2 = stream_load(io.c2 + gi);
-    v.c3 = stream_load(io.c3 + gi);
-    v.c4 = stream_load(io.c4 + gi);
-    v.c5 = stream_load(io.c5 + gi);
-    v.sigma = stream_load(io.sigma + gi);
+    v.P_b = io.P_b[gi];
+    v.c0 = io.c0[gi];
+    v.c1 = io.c1[gi];
+    v.c2 = io.c2[gi];
+    v.c3 = io.c3[gi];
+    v.c4 = io.c4[gi];
+    v.c5 = io.c5[gi];
+    v.sigma = io.sigma[gi];
     if constexpr (COUPLED) {
-        v.x0 = stream_load(cio.V_a + gi);
-        v.x1 = stream_load(cio.T_e + gi);
-        v.x2 = stream_load(cio.V_vac + gi);
-        v.x3 = stream_load(cio.Pstar + gi);
-        v.x4 = stream_load(cio.P_T + gi);
-        v.x5 = stream_load(cio.mdot_a + gi);
-        v.x6 = stream_load(cio.a_1 + gi);
+        v.x0 = cio.V_a[gi];
+        v.x1 = cio.T_e[gi];
+        v.x2 = cio.V_vac[gi];
+        v.x3 = cio.Pstar[gi];
+        v.x4 = cio.P_T[gi];
+        v.x5 = cio.mdot_a[gi];
+        v.x6 = cio.a_1[gi];
     } else {
-        v.x0 = stream_load(io.I_B0 + gi);
-        v.x1 = io.T ? stream_load(io.T + gi) : 0.0;
+        v.x0 = io.I_B0[gi];
+        v.x1 = io.T ? io.T[gi] : 0.0;
         v.x2 = v.x3 = v.x4 = v.x5 = v.x6 = 0.0;
     }
     return v;
@@ -240,14 +189,13 @@ __device__ __forceinline__ SampleIn<true> generate_sample(const McDesign& mc, co
 //               (j_ion in the rounds, jion_records_store; the others in the epilogue, system_epilogue_store)
 // LDS map (doubles): shared by the workgroup: simpson[96][2] | dpoly[32*12];  per wave: params[NROWS][64] |
 // tile[S*91] | 2 (sink).  The Simpson table is padded with zero weights to L*CH <= 96 entries so the angle loop
-// needs no branch.  The den/num partial sums of a round reuse the rows of `params` that the round has consumed.
+// needs no branch (NSIMP, TABLE_DOUBLES: csrc/pem_plume.h).  The den/num partial sums of a round reuse the rows of
+// `params` that the round has consumed.
 // ---------------------------------------------------------------------------------------------
 constexpr int NPARAM = 9;   // X1 X2 jcex | r0 G E (beam 1) | r0 G E (beam 2)
-constexpr int NSIMP = 96;   // >= L*CH for L in {2, 4, 8}
 constexpr int WPB = 4;      // waves per workgroup (they share the two tables and nothing else)
 template <int L>
 constexpr int param_rows() { return 2 * L > NPARAM ? 2 * L : NPARAM; }   // rows 2c, 2c+1 are reused for the Simpson partials
-constexpr int TABLE_DOUBLES = 2 * NSIMP + PEM_NDI * PEM_NDC;
 constexpr int QPOLY_DOUBLES = (PEM_NDI + PEM_NQB) * PEM_NDC * 2;
 template <int L, int JMODE>
 constexpr int wave_lds_doubles() {
@@ -257,33 +205,10 @@ constexpr int wave_lds_doubles() {
 template <int L, int JMODE>
 constexpr int fast_lds_doubles() { return TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>(); }
 
-// Order LDS traffic inside ONE wave (after the table load a wave only ever reads LDS it wrote itself): the LDS
-// unit executes a wave's DS instructions in issue order, so only the compiler has to be kept from reordering them.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// 16-byte store of the write-once profile stream.  Non-temporal: measured 227.6 -> 190.7 us per 1.25e6-sample
-// launch against plain stores, interleaved A/B (tools/ab_bench.py); the same hint on the small input
-// loads or on the per-sample QoI stores is slower and is not used.
-#ifndef PEM_NT_STORES
-#define PEM_NT_STORES 1
-#endif
 // tuning knobs of the fused modes (file scope: a #define inside a function body does not survive -save-temps)
 #ifndef PEM_LOGLIK_MU
 #define PEM_LOGLIK_MU 2       // measurement records in flight per lane in the fused likelihood mode
 #endif
-__device__ __forceinline__ void stream_store(f64x2 v, f64x2* dst) {
-#if PEM_NT_STORES
-    __builtin_nontemporal_store(v, dst);
-#else
-    *dst = v;
-#endif
-}
 
 // LDS views of one wave
 struct WaveLds {
@@ -371,20 +296,9 @@ struct NoCount {};
 // Inlined into the (rolled) rounds.  Its first version, inlined with every loop unrolled, cost the kernel 140 registers and one wave
 // per SIMD, so it went out of line -- where the premask variant saved two callee-saved registers on the stack per call (8 bytes
 // of scratch).  With the sample loops rolled in groups of four the inlined form fits two waves per SIMD (209-228 registers, no
-// scratch) and measures the same (5.13-5.21 against 5.18-5.22 ms per 1e7-sample campaign): -DPEM_COUNT_INLINE=0 is the other form.
-#ifndef PEM_COUNT_INLINE
-#define PEM_COUNT_INLINE 1
-#endif
-#if PEM_COUNT_INLINE
-#define PEM_COUNT_LINKAGE __forceinline__
-#else
-#define PEM_COUNT_LINKAGE __attribute__((noinline))
-#endif
+// scratch) and measures the same (5.13-5.21 against 5.18-5.22 ms per 1e7-sample campaign).
 template <int NQ, int S, bool FULL, bool PM>
-__device__ PEM_COUNT_LINKAGE unsigned count_round(unsigned ctx_off, unsigned tile_off, unsigned cnt, int lane, int rows, long long first) {
-#if defined(PEM_COUNT_EXP) && PEM_COUNT_EXP == 1
-    return cnt;
-#endif
+__device__ __forceinline__ unsigned count_round(unsigned ctx_off, unsigned tile_off, unsigned cnt, int lane, int rows, long long first) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const CountCtx ctx = *reinterpret_cast<const CountCtx*>(smem_raw + ctx_off);
     const uint2* tab = reinterpret_cast<const uint2*>(smem_raw + ctx.tab_off);
@@ -502,9 +416,6 @@ __device__ PEM_COUNT_LINKAGE unsigned count_round(unsigned ctx_off, unsigned til
             row_uncertain[lane] = (uint8_t)row_u;
         }
     }
-#if defined(PEM_COUNT_EXP) && PEM_COUNT_EXP == 2
-    bits = 0;
-#endif
     // The records: {key, angle} (which of the angle's brackets holds the key is found again by the passes over the records: they
     // see 4 % of the values).  Two per lane and turn -- the reads of the tile, and the stores, of both are in flight together --
     // appended behind the wave's count by however many lanes have one.
@@ -591,12 +502,6 @@ __device__ __forceinline__ double* pred_row(const WaveLds& m, long long t, unsig
     return m.pred + ((t * WAVE) / n_cond + (long long)(u / (unsigned)n_cond)) * m.ld_pred;
 }
 
-// u_ion grid node c of sim_hallthruster.jl:46-47, z = range(z0, z1, length = ncells), and the denominator of u_ion there:
-// one expression for thruster_uion_kernel and the fused multi-QoI mode, so that both see the same node values
-__device__ __forceinline__ double uion_z(double z0, double z1, int ncells, int c) {
-    return z0 + (z1 - z0) * ((double)c / (double)(ncells - 1));
-}
-__device__ __forceinline__ double uion_den(double z) { return 1.0 + exp(-100.0 * (z - 0.04)); }
 
 // JMODE 6 epilogue, one lane per sample: the V_cc, thrust and u_ion records of condition `cond` added to `ll` (the sample's j_ion
 // sum).  A kind without records adds nothing -- whatever that part of the model is (a NaN v_exh of V_cc > V_a included).
@@ -729,11 +634,7 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
         // and one wave per SIMD)
         // (the reduced-QoI mode takes this loop for the tiles that hold a sample the tables do not cover -- none under the priors:
         // rolled, with a rolled angle loop, it fits the three waves per SIMD that mode is compiled for; unrolled it spilled there)
-#if defined(PEM_COUNT_EXP) && PEM_COUNT_EXP == 3
-        constexpr int ROUND_UNROLL = L;
-#else
         constexpr int ROUND_UNROLL = (NQ > 0 || JMODE == 0) ? 1 : L;
-#endif
         constexpr int ANGLE_UNROLL = JMODE == 0 ? 1 : CH;
 #pragma unroll ROUND_UNROLL
         for (int round = 0; round < L; ++round) {
@@ -936,13 +837,13 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     }
     if (live) {
         // (the record predictions take V_cc, div_angle and T_c as optional outputs)
-        if (JMODE != 7 || io.div) stream_store1(acos(cos_div), io.div + g);
-        if (have_T && (JMODE != 7 || io.Tc)) stream_store1(thrust * cos_div, io.Tc + g);
+        if (JMODE != 7 || io.div) io.div[g] = acos(cos_div);
+        if (have_T && (JMODE != 7 || io.Tc)) io.Tc[g] = thrust * cos_div;
         if (io.invalid) io.invalid[g] = (uint8_t)((inv_mask >> lane) & 1);
         if constexpr (COUPLED) {
-            if (JMODE != 7 || cio.V_cc) stream_store1(V_cc, cio.V_cc + g);
-            if (cio.I_B0) stream_store1(I_B0, cio.I_B0 + g);
-            if (cio.T) stream_store1(thrust, cio.T + g);
+            if (JMODE != 7 || cio.V_cc) cio.V_cc[g] = V_cc;
+            if (cio.I_B0) cio.I_B0[g] = I_B0;
+            if (cio.T) cio.T[g] = thrust;
         }
     }
     wave_lds_sync();  // params are rewritten by the next tile
@@ -1147,854 +1048,14 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// general path: any number of radii, one lane per sample, plain strided stores.  Used for
-// sweep_radius arrays (tests/test_plume.py:31 uses 25 radii); not the benchmarked configuration.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void plume_generic_kernel(PlumeIO io, const double* __restrict__ radii, int R) {
-    const long long g = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= io.n) return;
-    const double c0 = io.c0[g], c1 = io.c1[g];
-    const PlumeSetup ps = plume_setup(io.P_b[g], c1, io.c2[g], io.c3[g], io.c4[g], io.c5[g], io.torr2pa);
-    const double n_neutral = ps.n_neutral, a1 = ps.a1, a2 = ps.a2;
-    const double sigma = io.sigma[g], I_B0 = io.I_B0[g];
-    const double u1 = 1.0 / (a1 * a1), u2 = 1.0 / (a2 * a2);
-    const double A1 = (1.0 - c0) / normaliser(a1, u1, PEM_DPOLY);
-    const double A2 = c0 / normaliser(a2, u2, PEM_DPOLY);
-    constexpr double H = HALF_PI / 90.0;
-    const double s1 = (H * H) * u1, s2 = (H * H) * u2;
-    const double r10 = exp(-s1), r20 = exp(-s2), q1 = exp(-2.0 * s1), q2 = exp(-2.0 * s2);
-    const bool have_T = io.T != nullptr;
-    const double thrust = have_T ? io.T[g] : 0.0;
-
-    int invalid = (a1 <= 0.0) ? 1 : 0;
-    // `literal`: the Gaussians by direct exp() instead of the recurrence -- the sample is redone that way when pass 0
-    // finds a value below 1e-290 / non-positive or a non-finite amplitude (the deep tail, see exact_chunk above)
-    bool literal = false, uncertain = false;
-    for (int pass = 0; pass < 2; ++pass) {  // pass 0: integrals + invalid flag; pass 1: profile stores
-        for (int r = 0; r < R; ++r) {
-            const double rad = radii[r];
-            const double decay = exp(-rad * n_neutral * sigma);
-            const double j_cex = I_B0 * (1.0 - decay) / (2.0 * PEM_PI * (rad * rad));
-            const double base = I_B0 * decay / (rad * rad);
-            const double B1 = base * A1, B2 = base * A2;
-            if (!__builtin_isfinite(B1) || !__builtin_isfinite(B2)) uncertain = true;
-            double e1 = (a1 == 0.0) ? __builtin_nan("") : 1.0, e2 = e1, r1 = r10, r2 = r20, den = 0.0, num = 0.0;
-            for (int k = 0; k < NANG; ++k) {
-                if (literal) {
-                    const double alpha = k == NANG - 1 ? HALF_PI : (double)k * H;
-                    const double t1 = alpha / a1, t2 = alpha / a2;
-                    e1 = exp(-(t1 * t1));
-                    e2 = exp(-(t2 * t2));
-                }
-                const double f = B1 * e1 + B2 * e2;
-                const double ji = f + j_cex;
-                if (pass == 0) {
-                    invalid |= (ji <= 0.0) ? 1 : 0;
-                    if (ji < 1e-290) uncertain = true;
-                    den = fma(PEM_SIMPSON_CDEN[k], f, den);
-                    num = fma(PEM_SIMPSON_CNUM[k], f, num);
-                } else {
-                    io.j_ion[((size_t)g * NANG + k) * R + r] = invalid ? 1e-20 : ji;
-                }
-                e1 *= r1;
-                r1 *= q1;
-                e2 *= r2;
-                r2 *= q2;
-            }
-            if (pass == 0) {
-                double cos_div = num / den;
-                if (cos_div == __builtin_inf()) cos_div = __builtin_nan("");
-                io.div[(size_t)g * R + r] = acos(cos_div);
-                if (have_T) io.Tc[(size_t)g * R + r] = thrust * cos_div;
-            }
-        }
-        if (pass == 0 && uncertain && !literal) {   // redo pass 0 literally; pass 1 then stores the literal values
-            literal = true;
-            invalid = (a1 <= 0.0) ? 1 : 0;
-            pass = -1;
-        }
-    }
-    if (io.invalid) io.invalid[g] = (uint8_t)invalid;
-}
-
-// ---------------------------------------------------------------------------------------------
-// sweep_radius arrays, 2 <= R <= RADII_MAX: one WAVE per sample.  For a sample the (91, R) block of j_ion is the outer
-// product  e1[k] B1[r] + e2[k] B2[r] + j_cex[r]  and is contiguous in memory: the wave computes the two Gaussians once
-// (91 direct exp() each -- literally the reference's expression, so its deep tail comes for free), the per-radius
-// amplitudes with lane = radius, and then streams the block with lane = linear index, 512 contiguous bytes per store,
-// deciding plume.py:105 on the way.  The divergence integrals are linear in the amplitudes: four Simpson sums of the two
-// Gaussians per sample, combined per radius.  The lane-per-sample
-// kernel above writes the same block with a stride of 91 R doubles between lanes: 251 GB/s at R = 25 against
-// this kernel's several TB/s (tools/radii_probe.py).
-// ---------------------------------------------------------------------------------------------
-constexpr int RADII_MAX = 256;
-struct RadiiArg {   // the sweep radii travel in the kernel arguments: no device allocation, no copy to wait for
-    double r[RADII_MAX];
-};
-__global__ __launch_bounds__(BLOCK) void plume_radii_kernel(PlumeIO io, RadiiArg radii_arg, int R, int ts) {
-#pragma clang fp contract(off)
-    __shared__ double lds_all[BLOCK / WAVE][2 * 96 + 3 * RADII_MAX];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* e1 = lds_all[wave];
-    double* e2 = e1 + 96;
-    double* B1 = e2 + 96;
-    double* B2 = B1 + RADII_MAX;
-    double* JC = B2 + RADII_MAX;
-    const long long nwaves = (long long)gridDim.x * (BLOCK / WAVE);
-    const bool have_T = io.T != nullptr;
-    const int step_r = WAVE % R, step_k = WAVE / R;
-    // A wave takes `ts` (<= 64) consecutive samples at a time: their parameters are computed once, one lane per sample
-    // (coalesced input loads), and handed to the whole wave by shuffles as it walks through the blocks.  The host picks
-    // ts = 64 for large batches and smaller tiles when there would otherwise be too few of them to fill the chip.
-    const long long ntiles = (io.n + ts - 1) / ts;
-    for (long long t = (long long)blockIdx.x * (BLOCK / WAVE) + wave; t < ntiles; t += nwaves) {
-    const long long gl = (lane < ts && t * ts + lane < io.n) ? t * ts + lane : io.n - 1;    // idle lanes repeat the last sample
-    const double c0_l = io.c0[gl], c1_l = io.c1[gl];
-    const PlumeSetup ps_l = plume_setup(io.P_b[gl], c1_l, io.c2[gl], io.c3[gl], io.c4[gl], io.c5[gl], io.torr2pa);
-    const double nn_l = ps_l.n_neutral, sigma_l = io.sigma[gl];
-    const double IB0_l = io.I_B0[gl];
-    const double a1_l = ps_l.a1, a2_l = ps_l.a2;
-    const double A1_l = (1.0 - c0_l) / normaliser(a1_l, 1.0 / (a1_l * a1_l), PEM_DPOLY);
-    const double A2_l = c0_l / normaliser(a2_l, 1.0 / (a2_l * a2_l), PEM_DPOLY);
-    const double thrust_l = have_T ? io.T[gl] : 0.0;
-    const int in_tile = (int)(io.n - t * ts < ts ? io.n - t * ts : ts);
-    for (int smp = 0; smp < in_tile; ++smp) {
-        const long long g = t * ts + smp;
-        const double a1 = __shfl(a1_l, smp), a2 = __shfl(a2_l, smp), A1 = __shfl(A1_l, smp), A2 = __shfl(A2_l, smp);
-        const double n_neutral = __shfl(nn_l, smp), sigma = __shfl(sigma_l, smp);
-        const double I_B0 = __shfl(IB0_l, smp), thrust = __shfl(thrust_l, smp);
-        // the two Gaussians of plume.py:99-100 on the 91-point grid, and their four Simpson functionals: the sums of
-        // plume.py:117-123 are linear in the amplitudes, den[r] = B1[r] sum_k w_k e1[k] + B2[r] sum_k w_k e2[k]
-        double s1d = 0.0, s1n = 0.0, s2d = 0.0, s2n = 0.0;
-        for (int k = lane; k < NANG; k += WAVE) {
-            const double alpha = k == NANG - 1 ? HALF_PI : (double)k * GRID_H;
-            const double t1 = alpha / a1, t2 = alpha / a2;
-            const double g1 = exp(-(t1 * t1)), g2 = exp(-(t2 * t2));
-            e1[k] = g1;
-            e2[k] = g2;
-            s1d = __builtin_fma(PEM_SIMPSON_CDEN[k], g1, s1d);
-            s1n = __builtin_fma(PEM_SIMPSON_CNUM[k], g1, s1n);
-            s2d = __builtin_fma(PEM_SIMPSON_CDEN[k], g2, s2d);
-            s2n = __builtin_fma(PEM_SIMPSON_CNUM[k], g2, s2n);
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) {
-            s1d += __shfl_xor(s1d, sh);
-            s1n += __shfl_xor(s1n, sh);
-            s2d += __shfl_xor(s2d, sh);
-            s2n += __shfl_xor(s2n, sh);
-        }
-        // per radius (lane = radius): amplitudes and the divergence angle
-        for (int r0 = 0; r0 < R; r0 += WAVE) {
-            const int r = r0 + lane;
-            if (r < R) {
-                const double rad = radii_arg.r[r];
-                const double decay = exp(-rad * n_neutral * sigma);
-                const double j_cex = I_B0 * (1.0 - decay) / (2.0 * PEM_PI * (rad * rad));
-                const double base = I_B0 * decay / (rad * rad);
-                const double b1 = base * A1, b2 = base * A2;
-                B1[r] = b1;
-                B2[r] = b2;
-                JC[r] = j_cex;
-                double num = b1 * s1n + b2 * s2n, den = b1 * s1d + b2 * s2d;
-                if (!(fabs(b1) + fabs(b2) < 1e300) || ((b1 < 0.0) != (b2 < 0.0) && b1 != 0.0 && b2 != 0.0)) {
-                    // Sum as the reference does (rare) when the amplitudes are near the overflow threshold (exp(+x) of a
-                    // negative density: its f_k = b1 e1[k] + b2 e2[k] overflows where the factored sums do not), or of
-                    // opposite sign (c0 outside [0, 1]): the reference cancels angle by angle, the factored form would
-                    // cancel two large sums at the end
-                    num = 0.0;
-                    den = 0.0;
-                    for (int k = 0; k < NANG; ++k) {
-                        const double f = b1 * e1[k] + b2 * e2[k];
-                        den = __builtin_fma(PEM_SIMPSON_CDEN[k], f, den);
-                        num = __builtin_fma(PEM_SIMPSON_CNUM[k], f, num);
-                    }
-                }
-                double cos_div = num / den;
-                if (cos_div == __builtin_inf()) cos_div = __builtin_nan("");
-                io.div[(size_t)g * R + r] = acos(cos_div);
-                if (have_T) io.Tc[(size_t)g * R + r] = thrust * cos_div;
-            }
-        }
-        wave_lds_sync();
-        // the (91, R) block, contiguous: lane = linear index k R + r; plume.py:105 is decided on the way
-        double* dst = io.j_ion + (size_t)g * NANG * R;
-        bool bad = a1 <= 0.0;
-        {
-            int k = lane / R, r = lane - k * R;
-            for (int idx = lane; idx < NANG * R; idx += WAVE) {
-                const double ji = (B1[r] * e1[k] + B2[r] * e2[k]) + JC[r];
-                bad |= ji <= 0.0;
-                __builtin_nontemporal_store(ji, dst + idx);
-                r += step_r;
-                k += step_k;
-                if (r >= R) {
-                    r -= R;
-                    ++k;
-                }
-            }
-        }
-        const bool invalid = __ballot(bad) != 0;
-        if (invalid)   // plume.py:106: the whole block becomes 1e-20 (rare: a second pass over it)
-            for (int idx = lane; idx < NANG * R; idx += WAVE) dst[idx] = 1e-20;
-        if (io.invalid && lane == 0) io.invalid[g] = (uint8_t)invalid;
-        wave_lds_sync();   // the staged rows are rewritten for the next sample
-    }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// sweep_radius arrays, RADII_SMALL < R <= RMID_MAX (tests/test_plume.py:31 uses 25): the recipe of the few-radii kernel below
-// applied to the wave-per-sample kernel above -- several samples in flight per wave, the block staged in LDS in final order,
-// 16-byte stores of whole contiguous runs.  G = 64 / R samples share a wave (7 at 9 radii ... 1 above 32): lane (grp, r) owns radius
-// r of sample grp, keeps its amplitudes in registers and walks the 91 angles; the two Gaussians of a sample (by recurrence from
-// three exp per beam and lane, literal exp() where the reference's own has left the normal range) are read from LDS as one
-// broadcast 16-byte word per angle.
-// What the lane produces -- b1[r] e1[k] + b2[r] e2[k] + j_cex[r], the Simpson sums of plume.py:117-123 taken angle by angle as the
-// reference takes them -- goes to an LDS tile laid out as j_ion is, `kc` rows of every sample at a time (8 KB per wave), and
-// leaves as runs of kc R contiguous doubles: one leading 8-byte store where a run starts on an odd double (the LDS copy is
-// placed with the same parity), then 1 KiB per instruction.  Against the kernel above this halves the LDS reads per value
-// (2.5 instead of 5), removes the per-value index arithmetic and never assembles a cache line from 8-byte pieces.
-// ---------------------------------------------------------------------------------------------
-// A run of `len` doubles from LDS to `dst`, the whole wave on it.  `from` has the 16-byte parity of `dst` (the LDS copy is placed
-// so).  Store instructions that cover WHOLE 128-byte lines are what the memory system wants: with every instruction straddling
-// a line boundary the same kernels run a quarter slower (block sizes 91 R x 8 bytes: 4.65 TB/s at R = 32, 3.39 at R = 33;
-// profiles/radii_mid_r03.txt).  So: the doubles up to the next line boundary as one partial instruction of 8-byte stores, then
-// 16 bytes per lane, 1 KiB per instruction, line-aligned; an odd double left at the end goes out alone.
-__device__ __forceinline__ void stream_run(const double* from, double* dst, int len, int lane) {
-#if defined(PEM_RMID_EXP) && PEM_RMID_EXP == 1     // experiment: the phases without their stores (tools/rmid_ab_probe.py)
-    if (len >= 0) return;
-#endif
-    int head = (int)((0 - (reinterpret_cast<uintptr_t>(dst) >> 3)) & 15);
-    head = head < len ? head : len;
-    if (lane < head) __builtin_nontemporal_store(from[lane], dst + lane);
-    const int body = (len - head) >> 1;
-    const f64x2* s2 = reinterpret_cast<const f64x2*>(from + head);
-    f64x2* d2 = reinterpret_cast<f64x2*>(dst + head);
-    for (int i = lane; i < body; i += WAVE) stream_store(s2[i], &d2[i]);
-    if (((len - head) & 1) && lane == 0) __builtin_nontemporal_store(from[len - 1], dst + (len - 1));
-}
-
-constexpr int RADII_SMALL = 8;                  // up to here: the recurrence kernel with the radii in registers (plume_rfew_kernel)
-constexpr int RMID_MAX = 64;
-constexpr int RMID_G_MAX = 5;                   // samples in flight per wave the staged kernel is instantiated for (R >= 11)
-// doubles of staged rows per wave: 10 KB -- with the Gaussians' 1.5 KB per sample what three workgroups per CU leave each other.
-// (Round 4, profiles/radii_mid_r04.txt: 512 / 768 / 1024 / 1280 doubles give 3.08 / 3.38 / 3.58 / 3.82 TB/s at 17 radii, 3.36 / 3.55 /
-// 3.73 / 3.85 at 25; radius counts whose rows are whole lines -- 32, 64 -- do not care.)
-#ifndef PEM_RMID_TILE_DOUBLES
-#define PEM_RMID_TILE_DOUBLES 1280
-#endif
-constexpr int RMID_TILE = PEM_RMID_TILE_DOUBLES;
-struct RadiiMidArg {
-    double r[RMID_MAX];
-};
-constexpr int RMID_ES = 97;                     // 16-byte words of E per sample: an odd stride, so that the G broadcast reads of an
-                                                // instruction fall on different banks (96: all on the same ones, G-way conflict)
-template <int G>
-constexpr int rmid_wave_doubles() { return ((G * RMID_ES * 2 + 1) & ~1) + RMID_TILE + 4; }   // E | tile | the samples' invalid flags (G <= 7 ints)
-
-#ifndef PEM_RMID_WAVES
-#define PEM_RMID_WAVES 3
-#endif
-// (round 4) S samples share a wave in P passes: the S R (sample, radius) pairs are dealt over the lanes pass by pass -- pair
-// f = 64 p + lane is radius f % R of sample f / R -- instead of 64 / R whole samples side by side with the lanes past their radii
-// idle.  With one pass (S = 64 / R) that is the round-3 kernel: 25 radii used 50 lanes of 64 and ran at 0.78 of what 32 radii
-// reach, 33 radii 33 lanes; five samples in two passes use 125 of 128 lane slots, three samples of 33 radii 99 of 128.
-// (four samples' Gaussians and rows, or a second pass' amplitudes, leave LDS / registers for two waves per SIMD only)
-template <int S, int P>
-constexpr int rmid_waves_per_simd() { return (S >= 4 || P >= 2) ? 2 : PEM_RMID_WAVES; }
-template <int S, int P>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(rmid_waves_per_simd<S, P>())))
-void plume_rmid_kernel(PlumeIO io, RadiiMidArg radii_arg, int R, int ts) {
-#pragma clang fp contract(off)
-    constexpr int RS = (RMID_TILE / S) & ~1;    // doubles of the tile per sample (even)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* mine = reinterpret_cast<double*>(smem_raw) + (size_t)wave * rmid_wave_doubles<S>();
-    double2* E = reinterpret_cast<double2*>(mine);   // [S][RMID_ES] {e1[k], e2[k]}
-    double* tile = mine + ((S * RMID_ES * 2 + 1) & ~1);   // [S][RS] staged rows (16-byte aligned)
-    int* badflag = reinterpret_cast<int*>(tile + RMID_TILE);   // [S] (the two spare doubles of the tile hold up to four; S <= 7: see rmid_wave_doubles)
-    // this lane's pairs: (sample of the group, radius) per pass; a lane past the S R pairs repeats the last pair and keeps nothing
-    int grp[P], rr[P];
-    bool on[P];
-    double rad[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int f = 64 * p + lane;
-        on[p] = f < S * R;
-        const int ff = on[p] ? f : S * R - 1;
-        grp[p] = ff / R;
-        rr[p] = ff - grp[p] * R;
-        rad[p] = radii_arg.r[rr[p]];
-    }
-    const int kc = (RS - 2) / R;                      // rows per chunk: kc R + 1 <= RS - 1
-    const long long nwaves = (long long)gridDim.x * (BLOCK / WAVE);
-    const bool have_T = io.T != nullptr;
-    const long long ntiles = (io.n + ts - 1) / ts;
-    for (long long t = (long long)blockIdx.x * (BLOCK / WAVE) + wave; t < ntiles; t += nwaves) {
-        // parameters of the tile's samples, one lane per sample (as plume_radii_kernel)
-        const long long gl = (lane < ts && t * ts + lane < io.n) ? t * ts + lane : io.n - 1;
-        const double c0_l = io.c0[gl], c1_l = io.c1[gl];
-        const PlumeSetup ps_l = plume_setup(io.P_b[gl], c1_l, io.c2[gl], io.c3[gl], io.c4[gl], io.c5[gl], io.torr2pa);
-        // (sigma, I_B0 and T of a sample are read again by its own lanes when its group comes up -- three loads that hit the cache --
-        // instead of being carried in registers across the tile: with them the kernel was eight registers over three waves per SIMD)
-        const double nn_l = ps_l.n_neutral;
-        const double a1_l = ps_l.a1, a2_l = ps_l.a2;
-        const double A1_l = (1.0 - c0_l) / normaliser(a1_l, 1.0 / (a1_l * a1_l), PEM_DPOLY);
-        const double A2_l = c0_l / normaliser(a2_l, 1.0 / (a2_l * a2_l), PEM_DPOLY);
-        const int in_tile = (int)(io.n - t * ts < ts ? io.n - t * ts : ts);
-        for (int s0 = 0; s0 < in_tile; s0 += S) {
-            // The Gaussians of the group's samples: the R lanes of a (sample, pass) take CHK consecutive angles each and advance
-            // e_k = exp(-(k h / a)^2) by the two-term recurrence of the R = 1 kernel (e_{k+1} = e_k r_k, r_{k+1} = r_k q) from
-            // three branch-free exp per beam.  A chunk in which the reference's own exp() has left the normal range (a value
-            // below 1e-290), or whose widths are not finite numbers, is evaluated literally as the reference does
-            // (plume.py:99-100), deep tail included.  (Straight into LDS: kept in a register array first the kernel spilled.)
-            if (lane < S) badflag[lane] = 0;
-            const int chk = (NANG + R - 1) / R;
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                const int k0 = rr[p] * chk;
-                const int sm = s0 + grp[p] < in_tile ? s0 + grp[p] : in_tile - 1;
-                const double a1g = __shfl(a1_l, sm), a2g = __shfl(a2_l, sm);
-                const double s1 = (GRID_H * GRID_H) * (1.0 / (a1g * a1g)), s2 = (GRID_H * GRID_H) * (1.0 / (a2g * a2g));
-                double e1 = exp_nonpos(-(double)(k0 * k0) * s1), r1 = exp_nonpos(-(double)(2 * k0 + 1) * s1);
-                double e2 = exp_nonpos(-(double)(k0 * k0) * s2), r2 = exp_nonpos(-(double)(2 * k0 + 1) * s2);
-                const double q1 = exp_nonpos(-2.0 * s1), q2 = exp_nonpos(-2.0 * s2);
-                double lo = __builtin_inf();
-                for (int i = 0; i < chk; ++i) {
-                    if (on[p] && k0 + i < NANG) E[grp[p] * RMID_ES + k0 + i] = make_double2(e1, e2);
-                    lo = fmin(lo, fmin(e1, e2));
-                    e1 *= r1;
-                    r1 *= q1;
-                    e2 *= r2;
-                    r2 *= q2;
-                }
-                if (!(lo >= 1e-290) || !__builtin_isfinite(s1) || !__builtin_isfinite(s2)) {
-                    for (int i = 0; i < chk; ++i) {
-                        const int k = k0 + i;
-                        const double alpha = k >= NANG - 1 ? HALF_PI : (double)k * GRID_H;
-                        const double t1 = alpha / a1g, t2 = alpha / a2g;
-                        if (on[p] && k < NANG) E[grp[p] * RMID_ES + k] = make_double2(exp(-(t1 * t1)), exp(-(t2 * t2)));
-                    }
-                }
-            }
-            // this lane's (sample, radius) pairs: amplitudes of plume.py:95-100
-            bool smp_on[P];
-            long long g[P];
-            double b1[P], b2[P], jcx[P], den[P], num[P], thrust[P];
-            bool bad[P];
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                smp_on[p] = on[p] && s0 + grp[p] < in_tile;
-                const int src = s0 + grp[p] < in_tile ? s0 + grp[p] : in_tile - 1;      // an idle pair repeats the last sample and stores nothing
-                g[p] = t * ts + src;
-                const double A1 = __shfl(A1_l, src), A2 = __shfl(A2_l, src);
-                const double n_neutral = __shfl(nn_l, src), sigma = io.sigma[g[p]];
-                const double I_B0 = io.I_B0[g[p]];
-                thrust[p] = have_T ? io.T[g[p]] : 0.0;
-                const double decay = exp(-rad[p] * n_neutral * sigma);
-                jcx[p] = I_B0 * (1.0 - decay) / (2.0 * PEM_PI * (rad[p] * rad[p]));
-                const double base = I_B0 * decay / (rad[p] * rad[p]);
-                b1[p] = base * A1;
-                b2[p] = base * A2;
-                den[p] = 0.0;
-                num[p] = 0.0;
-                bad[p] = false;
-            }
-            wave_lds_sync();
-            for (int k0 = 0; k0 < NANG; k0 += kc) {
-                const int rows = NANG - k0 < kc ? NANG - k0 : kc;
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    // where this pair's run starts in j_ion: the LDS copy gets the same parity
-                    const double* gdst = io.j_ion + ((size_t)g[p] * NANG + k0) * R;
-                    double* run = tile + grp[p] * RS + (int)((reinterpret_cast<uintptr_t>(gdst) >> 3) & 1);
-#if defined(PEM_RMID_EXP) && PEM_RMID_EXP == 2     // experiment: the stores without the rows' arithmetic (one row computed per chunk)
-                    if (on[p]) {
-                        for (int kk = 0; kk < (rows > 1 ? 1 : rows); ++kk) {
-#else
-                    if (on[p]) {
-#pragma unroll 4
-                        for (int kk = 0; kk < rows; ++kk) {
-#endif
-                            const int k = k0 + kk;
-                            const double2 ee = E[grp[p] * RMID_ES + k];
-                            const double f = b1[p] * ee.x + b2[p] * ee.y;      // j_beam + j_scat
-                            const double ji = f + jcx[p];                      // plume.py:102
-                            run[kk * R + rr[p]] = ji;
-                            den[p] = __builtin_fma(PEM_SIMPSON_CDEN[k], f, den[p]);
-                            num[p] = __builtin_fma(PEM_SIMPSON_CNUM[k], f, num[p]);
-                            bad[p] |= ji <= 0.0;
-                        }
-                    }
-                }
-                wave_lds_sync();
-                // the runs leave one after the other, the whole wave on each
-                for (int gi = 0; gi < S; ++gi) {
-                    if (s0 + gi >= in_tile) break;
-                    double* dst = io.j_ion + ((size_t)(t * ts + s0 + gi) * NANG + k0) * R;
-                    stream_run(tile + gi * RS + (int)((reinterpret_cast<uintptr_t>(dst) >> 3) & 1), dst, rows * R, lane);
-                }
-                wave_lds_sync();
-            }
-            // plume.py:105: a sample is invalid if alpha1 <= 0 or any of its values is <= 0 -- its pairs sit on several lanes and passes
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-                if (smp_on[p] && bad[p]) badflag[grp[p]] = 1;
-            wave_lds_sync();
-#pragma unroll
-            for (int p = 0; p < P; ++p) {
-                double cos_div = num[p] / den[p];   // plume.py:124-127
-                if (cos_div == __builtin_inf()) cos_div = __builtin_nan("");
-                const int src = s0 + grp[p] < in_tile ? s0 + grp[p] : in_tile - 1;
-                const bool invalid = __shfl(a1_l, src) <= 0.0 || badflag[grp[p]] != 0;
-                if (smp_on[p]) {
-                    io.div[(size_t)g[p] * R + rr[p]] = acos(cos_div);
-                    if (have_T) io.Tc[(size_t)g[p] * R + rr[p]] = thrust[p] * cos_div;
-                    if (io.invalid && rr[p] == 0) io.invalid[g[p]] = (uint8_t)invalid;
-                }
-            }
-            // plume.py:106: the whole block of an invalid sample becomes 1e-20 (rare: a second pass over it, the whole wave on each)
-            for (int gi = 0; gi < S; ++gi) {
-                if (s0 + gi >= in_tile) break;
-                const bool invalid = __shfl(a1_l, s0 + gi) <= 0.0 || badflag[gi] != 0;
-                if (invalid) {
-                    double* blk = io.j_ion + (size_t)(t * ts + s0 + gi) * NANG * R;
-                    for (int idx = lane; idx < NANG * R; idx += WAVE) blk[idx] = 1e-20;
-                }
-            }
-            wave_lds_sync();
-        }
-        wave_lds_sync();
-    }
-}
-
-struct RadiiSmallArg {
-    double r[RADII_SMALL];
-};
-
-// ---------------------------------------------------------------------------------------------
-// FEW radii by recurrence: the R = 1 fast path generalised (2 <= R <= RADII_SMALL).  The wave-per-sample kernel above is
-// bound by LATENCY, not by issue or HBM: a wave has one sample in flight, and every sample is a chain Gaussians -> LDS ->
-// wave reduction -> LDS -> block stream (5.4k cycles per sample measured at R = 2 where the instruction count says 1.3k;
-// moving the per-radius work out of that chain gained 10-19 %: profiles/radii_probe_r02.txt).  Here a wave works on 8 samples at a time as plume_r1_kernel does: lane (s, c) walks
-// angles k = 12 c .. 12 c + 11 of sample s, advancing the two Gaussians by the two-term recurrence (4 multiplies per
-// angle) from chunk starts that come from the same recurrence at stride 12; per angle it forms the R values
-// b1[r] e1 + b2[r] e2 + j_cex[r] from amplitudes it holds in registers and puts them -- R consecutive doubles -- into an LDS
-// tile laid out as j_ion is, which leaves as 1-KiB-per-instruction 16-byte stores when the round is done.  The Simpson functionals of the two Gaussians ride along (4 FMAs per angle) and are folded over
-// the 8 chunk lanes; cos_div / arccos / T_c of all (sample, radius) pairs of the 64-sample tile follow, one lane per pair.
-// "Equal to the reference" in the deep tail is kept as in the R = 1 path: a chunk with a value below 1e-290 (or <= 0, or
-// a non-finite amplitude) is re-evaluated literally with direct exp(); amplitudes of opposite sign or near overflow send
-// the pair's divergence integrals through the literal angle-by-angle sum.
-// LDS (doubles): shared: simpson[96][2] | dpoly[384];  per wave: params[8][64] | PB[64][R][3] | tile[8][91][R]
-// ---------------------------------------------------------------------------------------------
-constexpr int RF_L = 8, RF_S = WAVE / RF_L, RF_CH = 12;
-static_assert(RF_L * RF_CH >= NANG && RF_L * RF_CH <= NSIMP, "8 chunks of 12 angles cover the 91-point grid inside the padded table");
-// per wave: params[8][64] | PB[64][R][3] | tile[8][91][R] + 2; the workgroup has as many waves as fit 160 KB beside the tables
-template <int R>
-constexpr int rfew_wave_doubles() { return 8 * WAVE + 3 * WAVE * R + RF_S * NANG * R + 2; }
-template <int R>
-constexpr int rfew_waves() { return R <= 4 ? 4 : (R <= 6 ? 3 : 2); }
-
-template <int R>   // the number of radii is a compile-time constant: amplitudes and the values of two angles live in registers
-__global__ __launch_bounds__(WAVE * rfew_waves<R>()) void plume_rfew_kernel(PlumeIO io, RadiiSmallArg radii_arg) {
-    constexpr int RM = R;
-    // A round's 8 x 91 x R values go to an LDS tile in final order and leave as 1-KiB-per-instruction 16-byte stores, as in
-    // the R = 1 path.  (Stored straight from the angle loop instead -- 16 bytes per lane, 64 separate pieces per instruction
-    // -- the kernel ran at 2.1-2.4 TB/s; staged 3.7-4.7: profiles/radii_probe_r02.txt.)  The tile grows with R, so the
-    // workgroup shrinks: 4 waves up to R = 4, 3 up to 6, 2 for 7 and 8.
-    constexpr int NW = rfew_waves<R>();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    double* lds = reinterpret_cast<double*>(smem_raw);
-    double2* tab_simpson = reinterpret_cast<double2*>(lds);
-    double* tab_poly = lds + 2 * NSIMP;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    constexpr int per_wave = rfew_wave_doubles<R>();
-    double* params = lds + TABLE_DOUBLES + wave * per_wave;     // rows: a1 a2 | r0 G E (beam 1) | r0 G E (beam 2)
-    // a sample's rows 2..5 are free once its round has read them: they then carry its {s1d, s1n, s2d, s2n}
-    double* PB = params + 8 * WAVE;                             // [64][R][3] {b1, b2, j_cex}
-    double* tile = PB + 3 * WAVE * R;                           // [8][91][R] + 2
-    for (int i = tid; i < NSIMP; i += WAVE * NW)
-        tab_simpson[i] = i < NANG ? make_double2(PEM_SIMPSON_CDEN[i], PEM_SIMPSON_CNUM[i]) : make_double2(0.0, 0.0);
-    for (int i = tid; i < PEM_NDI * PEM_NDC; i += WAVE * NW) tab_poly[i] = PEM_DPOLY[i];
-    __syncthreads();
-
-    const int s = lane % RF_S, c = lane / RF_S, k0 = c * RF_CH;
-    const double2* my_w = tab_simpson + k0;
-    const bool have_T = io.T != nullptr;
-    const long long ntiles = (io.n + WAVE - 1) / WAVE;
-    const long long nwaves = (long long)gridDim.x * NW;
-    const size_t blk = (size_t)NANG * R;
-    for (long long t = (long long)blockIdx.x * NW + wave; t < ntiles; t += nwaves) {
-        const int in_tile = (int)(io.n - t * WAVE < WAVE ? io.n - t * WAVE : WAVE);
-        const long long gl = lane < in_tile ? t * WAVE + lane : io.n - 1;     // idle lanes repeat the last sample
-        // ------------------------------ prelude: one lane per sample ------------------------------
-        unsigned literal_l = 0;
-        {
-            const double c0_l = io.c0[gl];
-            const PlumeSetup ps = plume_setup(io.P_b[gl], io.c1[gl], io.c2[gl], io.c3[gl], io.c4[gl], io.c5[gl], io.torr2pa);
-            const double sigma_l = io.sigma[gl], IB0_l = io.I_B0[gl];
-            const double u1 = 1.0 / (ps.a1 * ps.a1), u2 = 1.0 / (ps.a2 * ps.a2);
-            const double A1 = (1.0 - c0_l) / normaliser(ps.a1, u1, tab_poly);
-            const double A2 = c0_l / normaliser(ps.a2, u2, tab_poly);
-            const double s1 = (GRID_H * GRID_H) * u1, s2 = (GRID_H * GRID_H) * u2;
-            params[0 * WAVE + lane] = ps.a1;
-            params[1 * WAVE + lane] = ps.a2;
-            params[2 * WAVE + lane] = exp_nonpos(-s1);
-            params[3 * WAVE + lane] = exp_nonpos(-(2.0 * RF_CH) * s1);
-            params[4 * WAVE + lane] = exp_nonpos(-(double)(RF_CH * RF_CH) * s1);
-            params[5 * WAVE + lane] = exp_nonpos(-s2);
-            params[6 * WAVE + lane] = exp_nonpos(-(2.0 * RF_CH) * s2);
-            params[7 * WAVE + lane] = exp_nonpos(-(double)(RF_CH * RF_CH) * s2);
-            for (int r = 0; r < R; ++r) {
-#pragma clang fp contract(off)
-                const double rad = radii_arg.r[r];
-                const double decay = exp(-rad * ps.n_neutral * sigma_l);
-                const double j_cex = IB0_l * (1.0 - decay) / (2.0 * PEM_PI * (rad * rad));
-                const double base = IB0_l * decay / (rad * rad);
-                const double b1 = base * A1, b2 = base * A2;
-                double* pb = PB + (lane * R + r) * 3;
-                pb[0] = b1;
-                pb[1] = b2;
-                pb[2] = j_cex;
-                if (!(fabs(b1) + fabs(b2) < 1e300) || ((b1 < 0.0) != (b2 < 0.0) && b1 != 0.0 && b2 != 0.0)) literal_l |= 1u << r;
-            }
-        }
-        const unsigned long long a1_nonpos = __ballot(params[0 * WAVE + lane] <= 0.0);
-        wave_lds_sync();
-        unsigned long long inv_mask = 0;
-        // ------------------------------ rounds: 8 samples, 8 chunk lanes each ------------------------------
-        for (int round = 0; round < RF_L; ++round) {
-            const int smp = round * RF_S + s;
-            const double r01 = params[2 * WAVE + smp], G1 = params[3 * WAVE + smp], E1 = params[4 * WAVE + smp];
-            const double r02 = params[5 * WAVE + smp], G2 = params[6 * WAVE + smp], E2 = params[7 * WAVE + smp];
-            double b1[RM], b2[RM], jc[RM];
-            bool finite = true;
-#pragma unroll
-            for (int r = 0; r < RM; ++r) {
-                const double* pb = PB + (smp * R + (r < R ? r : 0)) * 3;
-                b1[r] = pb[0];
-                b2[r] = pb[1];
-                jc[r] = pb[2];
-                finite = finite && __builtin_isfinite(b1[r]) && __builtin_isfinite(b2[r]);
-            }
-            // chunk start k0 = 12 c by the coarse recurrence: e_{k0} = E^(c^2), r_{k0} = r0 G^c
-            double e1 = 1.0, e2 = 1.0, rr1 = r01, rr2 = r02, rho1 = E1, rho2 = E2;
-            if (params[0 * WAVE + smp] == 0.0) e1 = e2 = __builtin_nan("");   // alpha1 = 0: exp(-(0/0)^2) is NaN in the reference
-            const double E1sq = E1 * E1, E2sq = E2 * E2;
-#pragma unroll
-            for (int i = 0; i < RF_L - 1; ++i) {
-                if (i < c) {
-                    e1 *= rho1;
-                    rho1 *= E1sq;
-                    rr1 *= G1;
-                    e2 *= rho2;
-                    rho2 *= E2sq;
-                    rr2 *= G2;
-                }
-            }
-            const double q1 = r01 * r01, q2 = r02 * r02;
-            double part[4] = {0.0, 0.0, 0.0, 0.0}, lo = __builtin_inf();
-            double* dst = tile + (size_t)s * blk + (size_t)k0 * R;
-            // The chunk's values are one run of 12 R consecutive doubles of the tile (laid out as j_ion is).  Two angles = 2 R doubles per iteration,
-            // stored as R 16-byte pieces.  For an odd R the run of an odd sample starts at an odd double (the start is
-            // (g 91 + 12 c) R doubles into a 16-byte aligned array): such a lane stores its first double on its own, then
-            // pieces shifted by one element (the last element of an iteration is carried into the next), and the last
-            // double on its own again -- selected per lane, so that every 16-byte store has all 64 lanes in it.
-            const bool mis = (R & 1) && (smp & 1);
-            double carry = 0.0;
-#pragma unroll 1
-            for (int jj = 0; jj < RF_CH; jj += 2) {
-                double ev[2 * RM];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const double2 w = my_w[jj + h];
-#pragma unroll
-                    for (int r = 0; r < RM; ++r) ev[h * RM + r] = fma(b1[r], e1, b2[r] * e2) + jc[r];
-                    part[0] = fma(w.x, e1, part[0]);
-                    part[1] = fma(w.y, e1, part[1]);
-                    part[2] = fma(w.x, e2, part[2]);
-                    part[3] = fma(w.y, e2, part[3]);
-                    e1 *= rr1;
-                    rr1 *= q1;
-                    e2 *= rr2;
-                    rr2 *= q2;
-                }
-                double* d = dst + (size_t)jj * R;
-                if (k0 + jj + 1 < NANG) {                  // both angles exist (all but the last iterations of the last chunk)
-#pragma unroll
-                    for (int i = 0; i < 2 * RM; ++i) lo = fmin(lo, ev[i]);
-                    {
-                        if constexpr ((R & 1) == 0) {
-#pragma unroll
-                            for (int q = 0; q < RM; ++q) *reinterpret_cast<f64x2*>(d + 2 * q) = f64x2{ev[2 * q], ev[2 * q + 1]};
-                        } else {
-                            if (mis && jj == 0) d[0] = ev[0];
-#pragma unroll
-                            for (int q = 0; q < RM; ++q) {
-                                f64x2 pr;
-                                pr.x = mis ? (q == 0 ? carry : ev[2 * q - 1]) : ev[2 * q];
-                                pr.y = mis ? ev[2 * q] : ev[2 * q + 1];
-                                if (!(mis && jj == 0 && q == 0)) *reinterpret_cast<f64x2*>(d + 2 * q - (mis ? 1 : 0)) = pr;
-                            }
-                            carry = ev[2 * RM - 1];
-                            if (mis && jj + 2 >= RF_CH) d[2 * RM - 1] = carry;      // the run ends here: its last double
-                        }
-                    }
-                } else {                                   // past 90 degrees: at most the first angle of the pair exists
-                    if (k0 + jj < NANG) {
-#pragma unroll
-                        for (int r = 0; r < RM; ++r) lo = fmin(lo, ev[r]);
-                        {
-                            if ((R & 1) && mis && jj > 0) d[-1] = carry;           // the carried double of the iteration before
-#pragma unroll
-                            for (int r = 0; r < RM; ++r) d[r] = ev[r];
-                        }
-                    } else if ((R & 1) && mis && jj > 0 && k0 + jj - 1 < NANG) {
-                        d[-1] = carry;
-                    }
-                    carry = 0.0;
-                    // (nothing further of this chunk exists; the recurrence runs on harmlessly)
-                }
-            }
-            // deep tail: where the reference's own exp() has left the normal range the chunk is evaluated literally
-            const bool uncertain = lo < 1e-290 || !finite;
-            if (__ballot(uncertain)) {
-                if (uncertain) {
-#pragma clang fp contract(off)
-                    const double a1s = params[0 * WAVE + smp], a2s = params[1 * WAVE + smp];
-                    part[0] = part[1] = part[2] = part[3] = 0.0;
-                    lo = __builtin_inf();
-                    for (int j = 0; j < RF_CH; ++j) {
-                        const int k = k0 + j;
-                        if (k >= NANG) break;
-                        const double alpha = k == NANG - 1 ? HALF_PI : (double)k * GRID_H;
-                        const double t1 = alpha / a1s, t2 = alpha / a2s;
-                        const double g1 = exp(-(t1 * t1)), g2 = exp(-(t2 * t2));
-                        for (int r = 0; r < R; ++r) {
-                            const double* pb = PB + (smp * R + r) * 3;
-                            const double ji = (pb[0] * g1 + pb[1] * g2) + pb[2];
-                            lo = fmin(lo, ji);
-                            dst[(size_t)j * R + r] = ji;
-                        }
-                        part[0] = __builtin_fma(my_w[j].x, g1, part[0]);
-                        part[1] = __builtin_fma(my_w[j].y, g1, part[1]);
-                        part[2] = __builtin_fma(my_w[j].x, g2, part[2]);
-                        part[3] = __builtin_fma(my_w[j].y, g2, part[3]);
-                    }
-                }
-            }
-            // fold the 8 chunk lanes of a sample: Simpson functionals and plume.py:105
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int sh = RF_S; sh < WAVE; sh <<= 1) part[q] += __shfl_xor(part[q], sh);
-            }
-            if (c == 0) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) params[(2 + q) * WAVE + smp] = part[q];
-            }
-            unsigned long long bad = __ballot(lo <= 0.0);
-#pragma unroll
-            for (int sh = RF_S; sh < WAVE; sh <<= 1) bad |= bad >> sh;
-            bad = (bad | (a1_nonpos >> (round * RF_S))) & ((1ull << RF_S) - 1);
-            inv_mask |= bad << (round * RF_S);
-            if ((bad >> s) & 1) {   // plume.py:106: the whole block of an invalid sample becomes 1e-20 (rare)
-                for (int j = 0; j < RF_CH; ++j)
-                    if (k0 + j < NANG)
-                        for (int r = 0; r < R; ++r) dst[(size_t)j * R + r] = 1e-20;
-            }
-            {
-                // the round's samples are one contiguous, 16-byte aligned piece of j_ion (round * 8 is even)
-                wave_lds_sync();
-                const long long first = t * WAVE + (long long)round * RF_S;
-                long long valid = (io.n - first) * (long long)blk;          // doubles of this round that exist
-                if (valid > (long long)RF_S * (long long)blk) valid = (long long)RF_S * (long long)blk;
-                // (for an odd R every other round starts 64 bytes into a 128-byte line: stream_run brings the body back onto
-                // line boundaries with one leading partial instruction)
-                if (valid > 0) stream_run(tile, io.j_ion + (size_t)first * blk, (int)valid, lane);
-                wave_lds_sync();   // the tile is rewritten by the next round
-            }
-        }
-        wave_lds_sync();
-        if (io.invalid && lane < in_tile) io.invalid[t * WAVE + lane] = (uint8_t)((inv_mask >> lane) & 1);
-        // ------------------------------ postlude: one lane per (sample, radius) pair ------------------------------
-        const int pairs = in_tile * R;
-        for (int idx = lane; idx < pairs; idx += WAVE) {
-            const int smp = idx / R, r = idx - smp * R;
-            const unsigned literal = (unsigned)__shfl((int)literal_l, smp);
-            const double* pb = PB + idx * 3;
-            const double s1d = params[2 * WAVE + smp], s1n = params[3 * WAVE + smp], s2d = params[4 * WAVE + smp], s2n = params[5 * WAVE + smp];
-            double num, den;
-            {
-#pragma clang fp contract(off)
-                num = pb[0] * s1n + pb[1] * s2n;
-                den = pb[0] * s1d + pb[1] * s2d;
-            }
-            if ((literal >> r) & 1) {   // the reference's own summation order (amplitudes of opposite sign / near overflow)
-#pragma clang fp contract(off)
-                const double a1s = params[0 * WAVE + smp], a2s = params[1 * WAVE + smp];
-                num = 0.0;
-                den = 0.0;
-                for (int k = 0; k < NANG; ++k) {
-                    const double alpha = k == NANG - 1 ? HALF_PI : (double)k * GRID_H;
-                    const double t1 = alpha / a1s, t2 = alpha / a2s;
-                    const double f = pb[0] * exp(-(t1 * t1)) + pb[1] * exp(-(t2 * t2));
-                    den = __builtin_fma(tab_simpson[k].x, f, den);
-                    num = __builtin_fma(tab_simpson[k].y, f, num);
-                }
-            }
-            double cos_div = num / den;
-            if (cos_div == __builtin_inf()) cos_div = __builtin_nan("");
-            const long long g = t * WAVE + smp;
-            io.div[(size_t)g * R + r] = acos(cos_div);
-            if (have_T) io.Tc[(size_t)g * R + r] = io.T[g] * cos_div;
-        }
-        wave_lds_sync();   // params / PB are rewritten by the next tile
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void cathode_kernel(long long n, const double* __restrict__ P_b,
-                                                        const double* __restrict__ V_a, const double* __restrict__ T_e,
-                                                        const double* __restrict__ V_vac,
-                                                        const double* __restrict__ Pstar,
-                                                        const double* __restrict__ P_T, double k,
-                                                        double* __restrict__ V_cc) {
-    const long long stride = (long long)gridDim.x * BLOCK;
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride)
-        V_cc[i] = cathode_vcc(P_b[i], V_a[i], T_e[i], V_vac[i], Pstar[i], P_T[i], k);
-}
-
-struct ThrusterOut {
-    double *I_B0, *I_d, *T, *eta_c, *eta_m, *eta_v, *eta_a, *v_exh;
-};
-
-__global__ __launch_bounds__(BLOCK) void thruster_kernel(long long n, const double* __restrict__ V_a,
-                                                         const double* __restrict__ V_cc,
-                                                         const double* __restrict__ mdot,
-                                                         const double* __restrict__ a_1, ThrusterOut o) {
-    const long long stride = (long long)gridDim.x * BLOCK;
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
-        const ThrusterQoI t = thruster_stage(V_a[i], V_cc[i], mdot[i], a_1[i]);
-        if (o.I_B0) o.I_B0[i] = t.I_B0;
-        if (o.I_d) o.I_d[i] = t.I_d;
-        if (o.T) o.T[i] = t.T;
-        if (o.eta_c) o.eta_c[i] = t.eta_c;
-        if (o.eta_m) o.eta_m[i] = t.eta_m;
-        if (o.eta_v) o.eta_v[i] = t.eta_v;
-        if (o.eta_a) o.eta_a[i] = t.eta_a;
-        if (o.v_exh) o.v_exh[i] = t.v_exh;
-    }
-}
-
-// u_ion(z) of sim_hallthruster.jl:46-47 on z = range(z0, z1, length = ncells): one row per sample, lanes along z
-__global__ __launch_bounds__(BLOCK) void thruster_uion_kernel(long long n, const double* __restrict__ v_exh, double z0,
-                                                              double z1, int ncells, double* __restrict__ z_out,
-                                                              double* __restrict__ u_ion) {
-    const long long total = n * ncells;
-    const long long stride = (long long)gridDim.x * BLOCK;
-    for (long long idx = (long long)blockIdx.x * BLOCK + threadIdx.x; idx < total; idx += stride) {
-        const long long i = idx / ncells;
-        const int c = (int)(idx - i * ncells);
-        const double z = uion_z(z0, z1, ncells, c);
-        if (i == 0 && z_out) z_out[c] = z;
-        u_ion[idx] = v_exh[i] / uion_den(z);
-    }
-}
-
-// The two filters hallthruster_jl applies to a finished run, batched (thruster.py:490-502):
-//   bit 0: thrust < 0 or beam current < 0 (non-physical);  bit 1: the ion velocity peaks before `threshold`
-// One wave per sample row: strided argmax (first maximum wins, as np.argmax) + wave reduction.
-__global__ __launch_bounds__(BLOCK) void thruster_filter_kernel(long long n, int ncells, const double* __restrict__ u_ion,
-                                                                const double* __restrict__ z, double threshold,
-                                                                int use_shock, const double* __restrict__ T,
-                                                                const double* __restrict__ I_B0,
-                                                                uint8_t* __restrict__ flags) {
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * BLOCK) >> 6;
-    for (long long i = wave; i < n; i += nwaves) {
-        int flag = 0;
-        if (lane == 0) {
-            const double t = T ? T[i] : 0.0, b = I_B0 ? I_B0[i] : 0.0;
-            flag = (t < 0.0 || b < 0.0) ? 1 : 0;
-        }
-        if (use_shock) {
-            double best = -__builtin_inf();
-            int where = 0x7fffffff;
-            bool any_nan = false;
-            for (int c = lane; c < ncells; c += 64) {
-                const double u = u_ion[i * ncells + c];
-                any_nan |= (u != u);
-                if (u > best) {
-                    best = u;
-                    where = c;
-                }
-            }
-            // np.argmax returns the first NaN if there is one; otherwise the first maximum
-            int nan_at = 0x7fffffff;
-            if (any_nan)
-                for (int c = lane; c < ncells; c += 64)
-                    if (u_ion[i * ncells + c] != u_ion[i * ncells + c]) {
-                        nan_at = c;
-                        break;
-                    }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double ob = __shfl_xor(best, m);
-                const int ow = __shfl_xor(where, m);
-                const int on = __shfl_xor(nan_at, m);
-                if (ob > best || (ob == best && ow < where)) {
-                    best = ob;
-                    where = ow;
-                }
-                nan_at = on < nan_at ? on : nan_at;
-            }
-            if (lane == 0) {
-                const int arg = nan_at != 0x7fffffff ? nan_at : (where == 0x7fffffff ? 0 : where);
-                if (z[arg] < threshold) flag |= 2;
-            }
-        }
-        if (lane == 0) flags[i] = (uint8_t)flag;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 std::atomic<int> g_lanes{4};
-std::atomic<int> g_device{-1};   // process default of the host-pointer entry points (pem_init); -1: the calling thread's
-
-// Host-pointer entry points run on the device given to pem_init, whichever thread calls them: a new thread's current
-// HIP device is 0, which is the wrong card for the worker threads of a one-process-per-GPU rank (gen_data.py:448-456
-// evaluates models on Thread pools).
-int use_default_device() {
-    const int d = g_device.load(std::memory_order_relaxed);
-    if (d >= 0) HIP_TRY(hipSetDevice(d));
-    return PEM_OK;
-}
 double g_angle_grid[NANG];
 std::once_flag g_grid_once;
-using pem::check_device;
-using pem::fail;
 
-// persistent grid of the fast kernel: workgroups of WPB waves, `per_cu` of them resident on every CU
-// Balanced rounds: a persistent wave takes tiles me, me + nwaves, ...; with the largest grid that fits, a 1.25e6-sample shard is
-// 9.54 tiles per wave -- ten rounds, the last one 54 % full and as long as a full one (a tile's duration is latency, not
-// bandwidth: tools/tail_probe.py).  The smallest grid with the same number of rounds fills every round instead.
-// Only where that costs little occupancy (>= 90 % of the slots stay in use): with two or three rounds the balanced grid is much
-// smaller than the full one and the kernel loses more to the missing parallelism than it gains at the tail (plume_radii_kernel,
-// 1e5 samples x 25 radii, 1.2 rounds: 560 us with the full grid, 655 us balanced; profiles/reconstruct_balanced_r02z.txt).
-// PEM_BALANCED_GRID=0 restores the full grid everywhere.
-size_t balanced_grid(size_t need, size_t cap) {
-    static const bool balanced = getenv("PEM_BALANCED_GRID") ? atoi(getenv("PEM_BALANCED_GRID")) != 0 : true;
-    if (need <= cap) return need;
-    if (!balanced || cap == 0) return cap;
-    const size_t rounds = (need + cap - 1) / cap;
-    const size_t g = (need + rounds - 1) / rounds;
-    return 10 * g >= 9 * cap ? g : cap;
-}
-
+// persistent grid of the fast kernel: workgroups of WPB waves, `per_cu` of them resident on every CU (balanced rounds:
+// balanced_grid, csrc/pem_common.h)
 // The grid of the R = 1 kernel, apart from the device query so that the host side can plan range launches with it
 // (pem_persistent_grid).  Two regimes for the HBM-bound modes (profile written), measured interleaved on one box in the
 // streaming regime (tools/grid_mode_ab.py, tools/launch_size_probe.py --walk; profiles/grid_modes_r03.txt):
@@ -2015,8 +1076,7 @@ long long persistent_grid(long long ntiles, long long cus, long long per_cu, boo
     if (!memory_bound) return g;
     // (the modes bound by instruction issue want every slot: balanced, the reduced-QoI launch takes 45.3 instead of 44.4 us and
     // the fused Monte-Carlo one 88 instead of 82 us; tools/grid_ab_probe.py)
-    static const bool one_shot = getenv("PEM_ONE_SHOT") ? atoi(getenv("PEM_ONE_SHOT")) != 0 : true;
-    if (one_shot && need > ONE_SHOT_ROUNDS * g) return need;
+    if (need > ONE_SHOT_ROUNDS * g) return need;
     return (long long)balanced_grid((size_t)need, (size_t)g);
 }
 
@@ -2068,9 +1128,6 @@ int r1_per_cu(size_t lds, long long* per_cu) {
         if (err != hipSuccess) return;
         const int regs = fa.numRegs > 0 ? ((fa.numRegs + 7) & ~7) : 256;
         by_regs = (512 / regs) * 4 / WPB;
-        if (getenv("PEM_DEBUG_OCCUPANCY"))
-            fprintf(stderr, "pem: plume_r1_kernel<%d,%d,%d,%d>: %d registers -> %d workgroups per CU\n", L, (int)COUPLED, JMODE,
-                    (int)MC, fa.numRegs, by_regs);
     });
     HIP_TRY(err);
     long long v = (long long)(160 * 1024 / lds);
@@ -2120,153 +1177,6 @@ int dispatch_lanes(const PlumeIO& io, const CoupledIO& cio, hipStream_t st) {
     }
 }
 
-template <int R>
-int launch_rfew(size_t n, hipStream_t st, const PlumeIO& io, const RadiiSmallArg& ra) {
-    constexpr int NW = rfew_waves<R>();
-    constexpr size_t lds = (size_t)(TABLE_DOUBLES + NW * rfew_wave_doubles<R>()) * 8;
-    static_assert(lds <= 160 * 1024, "the few-radii kernel's workgroup must fit the LDS");
-    if (lds > 64 * 1024) {
-        static pem::LdsAttrOnce attr;
-        HIP_TRY(attr.ensure(reinterpret_cast<const void*>(plume_rfew_kernel<R>)));
-    }
-    int cus = 256;
-    HIP_TRY(pem::device_cus(&cus));
-    const size_t per_cu = (160 * 1024) / lds < 2 ? 1 : 2;          // persistent: workgroups resident per CU
-    size_t grid = ((n + WAVE - 1) / WAVE + NW - 1) / NW;
-    grid = balanced_grid(grid, (size_t)cus * per_cu);     // (grids of 2 / 4 x the slots or one tile per wave: within 2 %, r03o)
-    hipLaunchKernelGGL(plume_rfew_kernel<R>, dim3((unsigned)grid), dim3(WAVE * NW), lds, st, io, ra);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// device workspace of the host-pointer entry points
-struct Workspace {
-    std::mutex mu;
-    void* buf = nullptr;
-    size_t cap = 0;
-    int device = -1;
-    int reserve(size_t bytes) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (buf && (cap < bytes || dev != device)) {
-            (void)hipFree(buf);
-            buf = nullptr;
-            cap = 0;
-        }
-        if (!buf) {
-            HIP_TRY(hipMalloc(&buf, bytes));
-            cap = bytes;
-            device = dev;
-        }
-        return PEM_OK;
-    }
-} g_ws;
-
-// carve 256-byte aligned arrays out of the workspace
-struct Carver {
-    unsigned char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base(static_cast<unsigned char*>(b)) {}
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + off);
-        off += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
-size_t padded(size_t bytes) { return (bytes + 255) & ~size_t(255); }
-
-// Host <-> device movement of one chunk of a host-pointer entry point.  A chunk whose whole workspace footprint fits
-// the pinned staging buffer is moved with ONE host-to-device and ONE device-to-host copy through a pinned mirror of the
-// workspace layout (inputs are carved first, outputs after them, so each side is one contiguous range): a call with
-// 15 input and 6 output arrays otherwise pays ~20 pageable-copy latencies (coupled, n = 1: 186 -> 61 us per call,
-// tools/latency_probe.py).  The two sides decide separately: inputs are staged when they fit, outputs when the whole
-// footprint does; what does not fit is copied array by array, where bandwidth is what matters.
-constexpr size_t STAGE_BYTES = size_t(2) << 20;
-struct Stage {
-    unsigned char* pin = nullptr;
-    bool tried = false;
-    unsigned char* get() {
-        if (!tried) {
-            tried = true;
-            void* p = nullptr;
-            if (hipHostMalloc(&p, STAGE_BYTES, hipHostMallocPortable) == hipSuccess) pin = static_cast<unsigned char*>(p);
-            else (void)hipGetLastError();
-        }
-        return pin;
-    }
-} g_stage;   // guarded by g_ws.mu
-
-// Small calls skip the copies altogether: the kernels read their inputs from the pinned staging buffer and write their results
-// to it over PCIe (hipHostMalloc memory is device-accessible at its host address and coherent), so a call is memcpy in, ONE launch,
-// a stream synchronisation, memcpy out -- without the two copy-engine round trips: the calls amisc makes while it trains (a few to a
-// few hundred samples) go from 33-35 to 27-29 us (cathode_coupling) and from 60-63 to 54-59 us (pem_v0_coupled), n = 1000: 113-148 ->
-// 95-108 us (tools/latency_probe.py, interleaved; profiles/latency_r04.txt).  At 560 KB of footprint (BASELINE configs[0]: 1e4 cathode
-// samples) the kernels' reads over the link cost what the copies saved: ZC_BYTES stays below that.  PEM_ZERO_COPY=0 switches it off.
-constexpr size_t ZC_BYTES = size_t(256) << 10;
-unsigned char* host_call_base(size_t footprint) {          // where a host-pointer call carves its arrays: g_ws.mu held, g_ws reserved
-    static const bool on = !(getenv("PEM_ZERO_COPY") && atoi(getenv("PEM_ZERO_COPY")) == 0);
-    if (on && footprint <= ZC_BYTES)
-        if (unsigned char* pin = g_stage.get()) return pin;
-    return static_cast<unsigned char*>(static_cast<void*>(g_ws.buf));
-}
-
-struct Mover {
-    unsigned char* ws;
-    unsigned char* pin;       // staging for the inputs, or nullptr: array-by-array copies
-    unsigned char* pin_out;   // staging for the outputs (needs the whole footprint to fit), or nullptr
-    size_t in_lo = ~size_t(0), in_hi = 0, out_lo = ~size_t(0), out_hi = 0;
-    struct Out {
-        void* host;
-        size_t off, bytes;
-    } outs[8];
-    int nout = 0;
-    // inputs are carved first: they end at `in_end`; the outputs end at `footprint`
-    Mover(void* workspace, size_t in_end, size_t footprint)
-        : ws(static_cast<unsigned char*>(workspace)),
-          pin(in_end <= STAGE_BYTES ? g_stage.get() : nullptr),
-          pin_out(footprint <= STAGE_BYTES ? pin : nullptr) {}
-    int in(const void* host, void* dev, size_t bytes) {
-        if (!pin) {
-            HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, nullptr));
-            return PEM_OK;
-        }
-        const size_t off = static_cast<unsigned char*>(dev) - ws;
-        memcpy(pin + off, host, bytes);
-        if (off < in_lo) in_lo = off;
-        if (off + bytes > in_hi) in_hi = off + bytes;
-        return PEM_OK;
-    }
-    int flush_in() {
-        if (pin && pin != ws && in_hi > in_lo) HIP_TRY(hipMemcpyAsync(ws + in_lo, pin + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, nullptr));
-        return PEM_OK;
-    }
-    int out(void* host, const void* dev, size_t bytes) {
-        if (!pin_out || nout == 8) {
-            HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, nullptr));
-            return PEM_OK;
-        }
-        const size_t off = static_cast<const unsigned char*>(dev) - ws;
-        outs[nout++] = Out{host, off, bytes};
-        if (off < out_lo) out_lo = off;
-        if (off + bytes > out_hi) out_hi = off + bytes;
-        return PEM_OK;
-    }
-    int finish() {
-        if (pin_out && pin_out != ws && out_hi > out_lo)       // (ws == pin: the zero-copy form -- the kernels wrote there)
-            HIP_TRY(hipMemcpyAsync(pin_out + out_lo, ws + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        for (int i = 0; i < nout; ++i) memcpy(outs[i].host, pin_out + outs[i].off, outs[i].bytes);
-        return PEM_OK;
-    }
-};
-#define PEM_TRY(expr)              \
-    do {                           \
-        if (int rc_ = (expr)) return rc_; \
-    } while (0)
-
 }  // namespace
 
 namespace pem {
@@ -2281,30 +1191,7 @@ char* error_buffer() {
 // =============================================================================================
 extern "C" {
 
-const char* pem_version(void) { return "hallthrusterpem_amd libpem_hip 0.1.0 (gfx950)"; }
-
 const char* pem_last_error(void) { return pem::error_buffer(); }
-
-int pem_device_count(void) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return cnt;
-}
-
-int pem_init(int device) {
-    if (int rc = check_device()) return rc;
-    HIP_TRY(hipSetDevice(device));
-    g_device.store(device, std::memory_order_relaxed);
-    return PEM_OK;
-}
-
-int pem_synchronize(pem_stream_t stream) {
-    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return PEM_OK;
-}
 
 int pem_set_lanes_per_sample(int lanes) {
     if (lanes == 0) lanes = 4;
@@ -2361,36 +1248,6 @@ const double* pem_angle_grid(void) {
     return g_angle_grid;
 }
 
-// ---- cathode ---------------------------------------------------------------------------------
-int pem_cathode_f64_dev(size_t n, const double* P_b, const double* V_a, const double* T_e, const double* V_vac,
-                        const double* Pstar, const double* P_T, double torr2pa, double* V_cc, pem_stream_t stream) {
-    if (n == 0) return PEM_OK;
-    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !V_cc) return fail(PEM_ERR_INVALID_ARG, "pem_cathode: NULL array");
-    if (int rc = check_device()) return rc;
-    size_t blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 256 * 8 * 4) blocks = 256 * 8 * 4;  // grid-stride beyond a few waves per SIMD
-    hipLaunchKernelGGL(cathode_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       (long long)n, P_b, V_a, T_e, V_vac, Pstar, P_T, torr2pa, V_cc);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-// ---- thruster test double ----------------------------------------------------------------------
-int pem_thruster_f64_dev(size_t n, const double* V_a, const double* V_cc, const double* mdot_a, const double* a_1,
-                         double* I_B0, double* I_d, double* T, double* eta_c, double* eta_m, double* eta_v,
-                         double* eta_a, double* v_exh, pem_stream_t stream) {
-    if (n == 0) return PEM_OK;
-    if (!V_a || !V_cc || !mdot_a || !a_1) return fail(PEM_ERR_INVALID_ARG, "pem_thruster: NULL input array");
-    if (int rc = check_device()) return rc;
-    size_t blocks = (n + BLOCK - 1) / BLOCK;
-    if (blocks > 256 * 8 * 4) blocks = 256 * 8 * 4;
-    ThrusterOut o{I_B0, I_d, T, eta_c, eta_m, eta_v, eta_a, v_exh};
-    hipLaunchKernelGGL(thruster_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       (long long)n, V_a, V_cc, mdot_a, a_1, o);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
 // ---- plume -------------------------------------------------------------------------------------
 int pem_plume_f64_dev(size_t n, int n_radii, const double* radii, double torr2pa, const double* P_b, const double* c0,
                       const double* c1, const double* c2, const double* c3, const double* c4, const double* c5,
@@ -2405,137 +1262,7 @@ int pem_plume_f64_dev(size_t n, int n_radii, const double* radii, double torr2pa
     hipStream_t st = static_cast<hipStream_t>(stream);
     PlumeIO io{(long long)n, torr2pa, radii[0], P_b, c0, c1, c2, c3, c4, c5, sigma_cex, I_B0, T, j_ion, div_angle, T_c, invalid};
     if (n_radii == 1 && aligned16(j_ion)) return dispatch_lanes<false, 1>(io, CoupledIO{}, st);
-
-    if (n_radii >= 2 && n_radii <= RADII_SMALL && aligned16(j_ion) && !getenv("PEM_RADII_GENERAL")) {
-        // few radii: eight samples per wave in flight, Gaussians by recurrence, profile stored from the angle loop
-        RadiiSmallArg ra;
-        for (int r = 0; r < RADII_SMALL; ++r) ra.r[r] = r < n_radii ? radii[r] : 1.0;
-        int rc = PEM_OK;
-        switch (n_radii) {
-            case 2: rc = launch_rfew<2>(n, st, io, ra); break;
-            case 3: rc = launch_rfew<3>(n, st, io, ra); break;
-            case 4: rc = launch_rfew<4>(n, st, io, ra); break;
-            case 5: rc = launch_rfew<5>(n, st, io, ra); break;
-            case 6: rc = launch_rfew<6>(n, st, io, ra); break;
-            case 7: rc = launch_rfew<7>(n, st, io, ra); break;
-            default: rc = launch_rfew<8>(n, st, io, ra); break;
-        }
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        return PEM_OK;
-    }
-    static const bool use_rmid = getenv("PEM_RADII_MID") ? atoi(getenv("PEM_RADII_MID")) != 0 : true;
-    // (read per call: tests walk through the instantiations)
-    int rmid_min = getenv("PEM_RMID_MIN") ? atoi(getenv("PEM_RMID_MIN")) : 13;
-    if (rmid_min < WAVE / RMID_G_MAX + 1) rmid_min = WAVE / RMID_G_MAX + 1;
-    if (use_rmid && n_radii >= rmid_min && n_radii > RADII_SMALL && n_radii <= RMID_MAX) {
-        // S samples in flight per wave in P passes, rows staged in LDS, line-aligned 16-byte stores (plume_rmid_kernel).  The pair
-        // (S, P) of the instantiated ones that fills the most lane slots, S R / (64 P): 25 radii -> five samples in two passes (125
-        // of 128; round 3: two samples in one, 50 of 64), 33 -> three in two (99 of 128; one sample before: 33 of 64).
-        // From 13 radii on (round 4, with the 10-KB tile: 13 / 14 / 15 / 16 radii 3.02 -> 3.35, 3.30 -> 3.73, 3.35 -> 3.57, 4.26 -> 4.38 TB/s
-        // against the wave-per-sample kernel below, interleaved; profiles/radii_mid_r04.txt); at 11 and 12 radii (PEM_RMID_MIN=11) it
-        // works and gains nothing.
-        // Instantiated: one pass.  Two- and three-pass packings (-DPEM_RMID_MULTIPASS=1) fill 86-98 % of the lane slots where one pass
-        // fills 52-80 %, and measured SLOWER at every radius count (25 radii: 3.25 against 3.69 TB/s, 33: 3.59 against 4.12, 44: 3.58
-        // against 4.33; profiles/radii_mid_r04.txt): more samples share the 8 KB of staged rows, so a sample's runs get shorter (200
-        // doubles instead of 500 at 25 radii) and the head / body / tail of a run and the two syncs around it are paid 12 times per
-        // sample instead of 5 -- the kernel's bound is that phase structure, not idle lanes.  What separates 32 / 40 / 48 / 64 radii
-        // (4.6-4.9 TB/s) from their neighbours (3.7-4.3) is the alignment of a sample's rows to 128-byte lines, not the lane count.
-#if defined(PEM_RMID_MULTIPASS) && PEM_RMID_MULTIPASS
-        static const int combos[][2] = {{1, 1}, {2, 1}, {3, 1}, {4, 1}, {5, 1}, {3, 2}, {5, 2}, {6, 2}, {7, 2}, {4, 3}, {6, 3}, {7, 3}};
-#else
-        static const int combos[][2] = {{1, 1}, {2, 1}, {3, 1}, {4, 1}, {5, 1}};
-#endif
-        int S = 1, P = 1;
-        double best = 0.0;
-        for (const auto& c : combos) {
-            if (c[0] * n_radii > WAVE * c[1] || (c[1] > 1 && c[0] * n_radii <= WAVE * (c[1] - 1))) continue;   // the pairs fill 64 (P - 1) + 1 .. 64 P slots
-            if ((RMID_TILE / c[0] - 2) / n_radii < 1) continue;                                               // a staged row per sample must fit
-            const double eff = (double)(c[0] * n_radii) / (WAVE * c[1]) - 0.02 * (c[1] - 1);                  // (a pass more has to pay for itself)
-            if (eff > best) {
-                best = eff;
-                S = c[0];
-                P = c[1];
-            }
-        }
-        if (const char* e = getenv("PEM_RMID_SP")) {                                   // tests / experiments: "S,P" of an instantiated pair
-            int es = 0, ep = 0;
-            if (sscanf(e, "%d,%d", &es, &ep) == 2 && es * n_radii <= WAVE * ep && (RMID_TILE / es - 2) / n_radii >= 1)
-                for (const auto& c : combos)
-                    if (c[0] == es && c[1] == ep) {
-                        S = es;
-                        P = ep;
-                    }
-        }
-        RadiiMidArg ra;
-        for (int r = 0; r < RMID_MAX; ++r) ra.r[r] = r < n_radii ? radii[r] : 1.0;
-        int ts = WAVE;                             // samples per wave tile: fewer when the batch is small
-        while (ts > 8 && (n + ts - 1) / ts < 256 * 32) ts >>= 1;
-        ts = ts / S * S;                           // whole groups only
-        if (ts < 2 * S) ts = 2 * S <= WAVE ? 2 * S : S;
-        if (const char* e = getenv("PEM_RMID_TS")) ts = atoi(e);                      // experiments
-        if (ts < 1 || ts > WAVE) return fail(PEM_ERR_INVALID_ARG, "pem_plume: PEM_RMID_TS must be 1..64");
-        const size_t ntiles = (n + ts - 1) / ts;
-        int cus = 256;
-        HIP_TRY(pem::device_cus(&cus));
-        size_t blocks = (ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-#define PEM_RMID_LAUNCH(S_, P_)                                                                                     \
-    do {                                                                                                            \
-        const size_t lds = (size_t)(BLOCK / WAVE) * rmid_wave_doubles<S_>() * 8;                                    \
-        size_t per_cu = (160 * 1024) / lds;                                                                         \
-        if (per_cu > (size_t)rmid_waves_per_simd<S_, P_>()) per_cu = rmid_waves_per_simd<S_, P_>();                 \
-        static pem::LdsAttrOnce attr;                          /* (four and five samples per wave: more than 64 KB) */ \
-        HIP_TRY(attr.ensure(reinterpret_cast<const void*>(plume_rmid_kernel<S_, P_>)));                             \
-        blocks = balanced_grid(blocks, (size_t)cus * per_cu);                                                       \
-        hipLaunchKernelGGL((plume_rmid_kernel<S_, P_>), dim3((unsigned)blocks), dim3(BLOCK), lds, st, io, ra, n_radii, ts); \
-    } while (0)
-        switch (S * 10 + P) {
-            case 11: PEM_RMID_LAUNCH(1, 1); break;
-            case 21: PEM_RMID_LAUNCH(2, 1); break;
-            case 31: PEM_RMID_LAUNCH(3, 1); break;
-            case 41: PEM_RMID_LAUNCH(4, 1); break;
-#if defined(PEM_RMID_MULTIPASS) && PEM_RMID_MULTIPASS
-            case 32: PEM_RMID_LAUNCH(3, 2); break;
-            case 52: PEM_RMID_LAUNCH(5, 2); break;
-            case 62: PEM_RMID_LAUNCH(6, 2); break;
-            case 72: PEM_RMID_LAUNCH(7, 2); break;
-            case 43: PEM_RMID_LAUNCH(4, 3); break;
-            case 63: PEM_RMID_LAUNCH(6, 3); break;
-            case 73: PEM_RMID_LAUNCH(7, 3); break;
-#endif
-            default: PEM_RMID_LAUNCH(5, 1); break;
-        }
-#undef PEM_RMID_LAUNCH
-        HIP_TRY(hipGetLastError());
-        return PEM_OK;
-    }
-    if (n_radii >= 2 && n_radii <= RADII_MAX) {
-        // wave per sample, coalesced (91, R) blocks, literal Gaussians (per 1e5..1e6 samples, tools/radii_probe.py: R = 25:
-        // 7415 -> 614 us, R = 5: 2089 -> 795 us, R = 3: 1262 -> 940 us, R = 2: 1183 -> 1314 us)
-        RadiiArg ra;
-        for (int r = 0; r < RADII_MAX; ++r) ra.r[r] = r < n_radii ? radii[r] : 1.0;
-        int ts = WAVE;                             // samples per wave tile: fewer when the batch is small
-        while (ts > 4 && (n + ts - 1) / ts < 256 * 20) ts >>= 1;
-        const size_t ntiles = (n + ts - 1) / ts;
-        size_t blocks = (ntiles + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-        blocks = balanced_grid(blocks, 256 * 5);   // persistent: 31 KB of LDS per workgroup, five per CU
-        hipLaunchKernelGGL(plume_radii_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, st, io, ra, n_radii, ts);
-        HIP_TRY(hipGetLastError());
-        return PEM_OK;
-    }
-    // lane-per-sample kernel (more than RADII_MAX radii; one radius with an unaligned j_ion): the radii go to the device
-    // through a small stream-ordered allocation, and -- `radii` being the caller's host memory -- this one path waits
-    // for the stream before it returns
-    double* d_radii = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_radii), sizeof(double) * n_radii, st));
-    HIP_TRY(hipMemcpyAsync(d_radii, radii, sizeof(double) * n_radii, hipMemcpyHostToDevice, st));
-    const size_t blocks = (n + BLOCK - 1) / BLOCK;
-    hipLaunchKernelGGL(plume_generic_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, st, io, d_radii, n_radii);
-    hipError_t le = hipGetLastError();
-    HIP_TRY(hipFreeAsync(d_radii, st));
-    HIP_TRY(le);
-    HIP_TRY(hipStreamSynchronize(st));
-    return PEM_OK;
+    return pem::launch_plume_radii(n, n_radii, radii, io, st);
 }
 
 // ---- coupled -----------------------------------------------------------------------------------
@@ -2604,8 +1331,10 @@ int pem_coupled_mc_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint32
     return j_ion ? launch_r1<4, true, 1, true>(io, cio, st, mc) : launch_r1<4, true, 0, true>(io, cio, st, mc);
 }
 
-// ---- coupled, fused Monte-Carlo + campaign statistics: see csrc/pem_qfused.h, pem_coupled_mc_stats_f64_dev below --------------
 }  // extern "C"
+
+// ---- coupled, fused Monte-Carlo + campaign statistics: what csrc/pem_campaign.hip (pem_coupled_mc_stats_f64_dev) launches through
+// csrc/pem_qfused.h
 
 namespace {
 
@@ -2681,221 +1410,6 @@ int launch_coupled_mc_count(const McLaunch& a, const CountIO& c, bool store_prof
 }  // namespace pem
 
 extern "C" {
-
-// ---- coupled, fused Monte-Carlo with the percentiles of the profile counted on the way (round 4) --------------------------------
-namespace {
-// The scalar QoIs' percentiles of a campaign, selected on a second host thread and stream while the calling thread takes the
-// profile through its pilot, its counting launch and the passes over its records (csrc/pem_quantile.hip keeps a second set of
-// buffers for it).  Two stages, each released on the host (a promise) and ordered on the device (an event): the scalars of the
-// pilot's samples exist once the pilot evaluation is under way -- the worker brackets the wanted ranks from them while the
-// counting launch runs -- and all of them once the counting launch (or, after a decline, the plain launch) is.
-struct ScalarJob {
-    struct Stage {
-        std::promise<int> go;                  // 1: `ev` marks the launch; 0: give up (an error on the calling thread)
-        std::future<int> gone;
-        bool signalled = false;
-        hipEvent_t ev = nullptr;
-        Stage() : gone(go.get_future()) {}
-        void signal(int v) {
-            if (!signalled) {
-                signalled = true;
-                go.set_value(v);
-            }
-        }
-        int launched(hipStream_t st) {         // after the launch has been enqueued on `st`
-            if (signalled) return PEM_OK;
-            HIP_TRY(hipEventRecord(ev, st));
-            signal(1);
-            return PEM_OK;
-        }
-        // the worker: block until the launch is under way, then make `side` wait for it
-        int await(hipStream_t side) {
-            if (gone.get() != 1) return fail(PEM_ERR_HIP, "pem_coupled_mc_stats (scalar selection): given up");
-            HIP_TRY(hipStreamWaitEvent(side, ev, 0));
-            return PEM_OK;
-        }
-    };
-    Stage pilot, full;
-    // The other direction: the counting launch must not START while the side selection's subsample passes are still running -- their
-    // histograms take most of a CU's LDS, a workgroup of the persistent counting grid that finds no room waits for a whole pass of its
-    // neighbours, and the launch takes 4 ms instead of 2.3 (seen in two calls of seven under the profiler, whose host threads are
-    // slow).  The worker marks the end of those passes (`side`: released by the worker, awaited by the calling thread).
-    Stage side;
-    std::thread worker;
-    std::function<void()> body;                // what the worker runs
-    bool started = false;
-    int rc = PEM_OK;
-    std::string error;
-    // Events and thread are made AFTER the pilot evaluation has been enqueued (McProducer::pilot): their 50-100 us of host time then
-    // pass while the GPU works instead of in front of the call's first kernel.
-    int start() {
-        if (started) return PEM_OK;
-        started = true;
-        HIP_TRY(hipEventCreateWithFlags(&pilot.ev, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&full.ev, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&side.ev, hipEventDisableTiming));
-        try {
-            worker = std::thread(body);
-        } catch (const std::exception& e) {    // (no thread to be had: nothing may leave a C entry point but its return code)
-            return fail(PEM_ERR_HIP, "pem_coupled_mc_stats: could not start the scalar selection's thread: %s", e.what());
-        }
-        return PEM_OK;
-    }
-    int join() {
-        pilot.signal(0);
-        full.signal(0);
-        if (worker.joinable()) worker.join();
-        for (Stage* s : {&pilot, &full, &side}) {
-            if (s->ev) (void)hipEventDestroy(s->ev);
-            s->ev = nullptr;
-        }
-        return rc;
-    }
-    ~ScalarJob() { (void)join(); }
-};
-
-// a stream of the library's own per device (created once)
-int side_stream(hipStream_t* out) {
-    static std::mutex mu;
-    static hipStream_t streams[64] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(PEM_ERR_INVALID_ARG, "device index out of range");
-    std::lock_guard<std::mutex> lock(mu);
-    // (a higher stream priority for the side work was measured and changes nothing: 3.85-3.92 ms per 1e7-sample campaign either way)
-    if (!streams[dev]) HIP_TRY(hipStreamCreateWithFlags(&streams[dev], hipStreamNonBlocking));
-    *out = streams[dev];
-    return PEM_OK;
-}
-
-struct McProducer : pem::FusedProducer {
-    pem::McLaunch a;
-    bool store_profile;
-    bool counted = false;                          // the counting launch is under way: every output but the percentiles gets written
-    ScalarJob* job = nullptr;
-    int pilot(size_t rows, double* dst, hipStream_t st) override {
-        pem::McLaunch p = a;                       // samples 0 .. rows-1 of the same design; their profile rows go to dst
-        p.n = rows;
-        p.j_ion = dst;
-        if (int rc = pem::launch_coupled_mc(p, st)) return rc;
-        if (!job) return PEM_OK;
-        if (int rc = job->start()) return rc;
-        return job->pilot.launched(st);            // (their scalars too: the side selection's subsample)
-    }
-    int waves(int nq, unsigned* w) override { return pem::coupled_count_waves(a.n, nq, store_profile, w); }
-    int count(const pem::CountIO& io, hipStream_t st) override {
-        if (job && job->worker.joinable() && job->side.gone.get() == 1) HIP_TRY(hipStreamWaitEvent(st, job->side.ev, 0));   // (see ScalarJob::side)
-        if (int rc = pem::launch_coupled_mc_count(a, io, store_profile, st)) return rc;
-        counted = true;
-        return job ? job->full.launched(st) : PEM_OK;    // (the side selection's passes over all samples may follow this launch)
-    }
-};
-}  // namespace
-
-int pem_coupled_mc_stats_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind, const double* a,
-                                 const double* b, double torr2pa, double radius, double* x_out, size_t ld, double* V_cc, double* I_B0,
-                                 double* T, double* j_ion, double* pilot_rows, double* div_angle, double* T_c, uint8_t* invalid, int nq,
-                                 const uint64_t* rank_prev, const uint64_t* rank_next, const double* gamma, double* q_out, double* q_scalars,
-                                 int* fused_ok, int q25, int q75, double iqr_factor, uint8_t* row_certain, uint8_t* row_uncertain,
-                                 int* premask_ok, pem_stream_t stream) {
-    if (!kind || !a || !b || !V_cc || !div_angle || !T_c || !rank_prev || !rank_next || !gamma || !q_out || !fused_ok)
-        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: NULL array");
-    if (!j_ion && !pilot_rows) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: without a profile array, room for the pilot rows is needed");
-    if (j_ion && !aligned16(j_ion)) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: j_ion must be 16-byte aligned");
-    if (pilot_rows && !aligned16(pilot_rows)) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: pilot_rows must be 16-byte aligned");
-    if (x_out && ld < n) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: leading dimension smaller than n");
-    if (nq < 1 || nq > PEM_QUANTILE_MAX_Q) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: 1 <= nq <= %d", PEM_QUANTILE_MAX_Q);
-    if (n < PEM_MC_STATS_MIN_N) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: at least %d samples", PEM_MC_STATS_MIN_N);
-    // q_scalars: V_cc, div_angle, T_c must then be rows 0, 1, 2 of one [3][row stride >= n] array (the reduced-QoI tensor)
-    const ptrdiff_t qstride = div_angle - V_cc;
-    if (q_scalars && (qstride < (ptrdiff_t)n || T_c - div_angle != qstride))
-        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_mc_stats: q_scalars needs V_cc, div_angle, T_c as equally spaced rows of one array");
-    if (int rc = check_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ScalarJob job;
-    McProducer prod;
-    if (q_scalars) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        hipStream_t side = nullptr;
-        if (int rc = side_stream(&side)) return rc;
-        job.body = [&job, dev, side, n, nq, V_cc, qstride, rank_prev, rank_next, gamma, q_scalars]() {
-            struct Release {                                             // (whatever happens: the calling thread is not left waiting)
-                ScalarJob& j;
-                ~Release() { j.side.signal(0); }
-            } release{job};
-            auto note = [&job](int rc) {
-                job.rc = rc;
-                if (rc != PEM_OK) job.error = pem_last_error();          // (the message lives in this thread's buffer)
-                return rc;
-            };
-            if (hipSetDevice(dev) != hipSuccess) {
-                (void)note(fail(PEM_ERR_HIP, "pem_coupled_mc_stats (scalar selection): hipSetDevice failed"));
-                return;
-            }
-            if (note(job.pilot.await(side))) return;
-            pem::SidePlan plan;
-            plan.ctx = &job;
-            plan.before_full = [](void* ctx, hipStream_t st) {
-                ScalarJob* j = static_cast<ScalarJob*>(ctx);
-                if (j->side.launched(st)) j->side.signal(0);             // the subsample's passes end here (on `st`, the side stream)
-                return j->full.await(st);
-            };
-            (void)note(pem::quantiles_side(n, 3, V_cc, 1, (size_t)qstride, nq, rank_prev, rank_next, gamma, q_scalars, side, &plan));
-        };
-        prod.job = &job;
-    }
-    prod.a.n = n;
-    prod.a.first_index = first_index;
-    prod.a.seed = seed;
-    prod.a.stream_id = stream_id;
-    for (int d = 0; d < 15; ++d) {
-        prod.a.kind[d] = kind[d];
-        prod.a.a[d] = a[d];
-        prod.a.b[d] = b[d];
-    }
-    prod.a.torr2pa = torr2pa;
-    prod.a.radius = radius;
-    prod.a.x_out = x_out;
-    prod.a.ld = ld;
-    prod.a.V_cc = V_cc;
-    prod.a.I_B0 = I_B0;
-    prod.a.T = T;
-    prod.a.j_ion = j_ion;
-    prod.a.div_angle = div_angle;
-    prod.a.T_c = T_c;
-    prod.a.invalid = invalid;
-    prod.store_profile = j_ion != nullptr;
-    if (row_certain && row_uncertain && premask_ok) {
-        prod.pm_q25 = q25;
-        prod.pm_q75 = q75;
-        prod.pm_factor = iqr_factor;
-        prod.pm_certain = row_certain;
-        prod.pm_uncertain = row_uncertain;
-    }
-    if (premask_ok) *premask_ok = 0;
-    *fused_ok = 0;
-    // with a profile array the pilot rows are its own first rows (the counting launch writes the same values there again)
-    if (int rc = pem::quantiles_fused(n, NANG, nq, rank_prev, rank_next, gamma, j_ion ? j_ion : pilot_rows, prod, q_out, fused_ok, st))
-        return rc;                                 // (~ScalarJob tells the worker to give up and joins it)
-    if (premask_ok) *premask_ok = (*fused_ok && prod.pm_done) ? 1 : 0;
-    if (!*fused_ok && !prod.counted) {
-        // declined before the counting launch (the fused form refused the call's shape), with nothing but the pilot's samples evaluated:
-        // the plain launch makes every output complete.  (Declined AFTER it -- unfit brackets, a rank outside its bracket, record
-        // overflow, a non-finite value -- the counting launch has written every output already; only the percentiles are missing.)
-        if (int rc = pem::launch_coupled_mc(prod.a, st)) return rc;
-        if (q_scalars) {
-            if (int rc = job.start()) return rc;
-            if (int rc = job.pilot.launched(st)) return rc;               // (no-ops for a stage that has been released)
-            if (int rc = job.full.launched(st)) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (q_scalars) {                               // (both stages released by now on every path that comes here)
-        if (int rc = job.join()) return fail(rc, "%s", job.error.c_str());
-    }
-    return PEM_OK;
-}
 
 // ---- coupled + likelihood fused: the profile never leaves the chip ------------------------------------------------
 int pem_coupled_loglik_f64_dev(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a,
@@ -2990,198 +1504,6 @@ int pem_coupled_mixed_dev(size_t n, double torr2pa, double radius, const double*
     PlumeIO io{(long long)n, torr2pa, radius, P_b, c0, c1, c2, c3, c4, c5, sigma_cex, nullptr, nullptr, nullptr, div_angle, T_c, invalid, j_ion_f32};
     CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, I_B0, T};
     return dispatch_lanes<true, 2>(io, cio, static_cast<hipStream_t>(stream));
-}
-
-// ---- thruster profile + filters ----------------------------------------------------------------------
-int pem_thruster_uion_f64_dev(size_t n, const double* v_exh, double z0, double z1, int ncells, double* z, double* u_ion,
-                              pem_stream_t stream) {
-    if (ncells < 2) return fail(PEM_ERR_INVALID_ARG, "pem_thruster_uion: need at least 2 grid points");
-    if (n == 0) return PEM_OK;
-    if (!v_exh || !u_ion) return fail(PEM_ERR_INVALID_ARG, "pem_thruster_uion: NULL array");
-    if (int rc = check_device()) return rc;
-    size_t blocks = (n * (size_t)ncells + BLOCK - 1) / BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(thruster_uion_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       (long long)n, v_exh, z0, z1, ncells, z, u_ion);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_thruster_filter_f64_dev(size_t n, int ncells, const double* u_ion, const double* z, double shock_threshold,
-                                int use_shock, const double* T, const double* I_B0, uint8_t* flags, pem_stream_t stream) {
-    if (n == 0) return PEM_OK;
-    if (!flags) return fail(PEM_ERR_INVALID_ARG, "pem_thruster_filter: NULL flags");
-    if (use_shock && (!u_ion || !z || ncells < 1)) return fail(PEM_ERR_INVALID_ARG, "pem_thruster_filter: shock filter needs u_ion and z");
-    if (int rc = check_device()) return rc;
-    size_t blocks = (n * 64 + BLOCK - 1) / BLOCK;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(thruster_filter_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       (long long)n, ncells, u_ion, z, shock_threshold, use_shock, T, I_B0, flags);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-// =============================================================================================
-// host-pointer entry points: stage through the device workspace in chunks
-// =============================================================================================
-int pem_cathode_f64(size_t n, const double* P_b, const double* V_a, const double* T_e, const double* V_vac,
-                    const double* Pstar, const double* P_T, double torr2pa, double* V_cc) {
-    if (n == 0) return PEM_OK;
-    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !V_cc) return fail(PEM_ERR_INVALID_ARG, "pem_cathode: NULL array");
-    if (int rc = check_device()) return rc;
-    if (int rc = use_default_device()) return rc;
-    std::lock_guard<std::mutex> lock(g_ws.mu);
-    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
-    if (int rc = g_ws.reserve(7 * padded(chunk * 8))) return rc;
-    unsigned char* const base = host_call_base(7 * padded(chunk * 8));
-    const double* in[6] = {P_b, V_a, T_e, V_vac, Pstar, P_T};
-    for (size_t off = 0; off < n; off += chunk) {
-        const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[7];
-        for (int i = 0; i < 6; ++i) d[i] = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        d[6] = cv.take<double>(chunk);
-        Mover mv(base, in_end, cv.off);
-        for (int i = 0; i < 6; ++i) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
-        PEM_TRY(mv.flush_in());
-        if (int rc = pem_cathode_f64_dev(m, d[0], d[1], d[2], d[3], d[4], d[5], torr2pa, d[6], nullptr)) return rc;
-        PEM_TRY(mv.out(V_cc + off, d[6], m * 8));
-        PEM_TRY(mv.finish());
-    }
-    return PEM_OK;
-}
-
-int pem_thruster_f64(size_t n, const double* V_a, const double* V_cc, const double* mdot_a, const double* a_1,
-                     double* I_B0, double* I_d, double* T, double* eta_c, double* eta_m, double* eta_v, double* eta_a,
-                     double* v_exh) {
-    if (n == 0) return PEM_OK;
-    if (!V_a || !V_cc || !mdot_a || !a_1) return fail(PEM_ERR_INVALID_ARG, "pem_thruster: NULL input array");
-    if (int rc = check_device()) return rc;
-    if (int rc = use_default_device()) return rc;
-    std::lock_guard<std::mutex> lock(g_ws.mu);
-    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
-    if (int rc = g_ws.reserve(12 * padded(chunk * 8))) return rc;
-    unsigned char* const base = host_call_base(12 * padded(chunk * 8));
-    const double* in[4] = {V_a, V_cc, mdot_a, a_1};
-    double* out[8] = {I_B0, I_d, T, eta_c, eta_m, eta_v, eta_a, v_exh};
-    for (size_t off = 0; off < n; off += chunk) {
-        const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double *di[4], *dout[8];
-        for (auto& p : di) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        for (int i = 0; i < 8; ++i) dout[i] = out[i] ? cv.take<double>(chunk) : nullptr;
-        Mover mv(base, in_end, cv.off);
-        for (int i = 0; i < 4; ++i) PEM_TRY(mv.in(in[i] + off, di[i], m * 8));
-        PEM_TRY(mv.flush_in());
-        if (int rc = pem_thruster_f64_dev(m, di[0], di[1], di[2], di[3], dout[0], dout[1], dout[2], dout[3], dout[4],
-                                          dout[5], dout[6], dout[7], nullptr))
-            return rc;
-        for (int i = 0; i < 8; ++i)
-            if (out[i]) PEM_TRY(mv.out(out[i] + off, dout[i], m * 8));
-        PEM_TRY(mv.finish());
-    }
-    return PEM_OK;
-}
-
-int pem_plume_f64(size_t n, int n_radii, const double* radii, double torr2pa, const double* P_b, const double* c0,
-                  const double* c1, const double* c2, const double* c3, const double* c4, const double* c5,
-                  const double* sigma_cex, const double* I_B0, const double* T, double* j_ion, double* div_angle,
-                  double* T_c, uint8_t* invalid) {
-    if (n_radii < 1 || !radii) return fail(PEM_ERR_INVALID_ARG, "pem_plume: need at least one sweep radius");
-    if (n == 0) return PEM_OK;
-    if (!P_b || !c0 || !c1 || !c2 || !c3 || !c4 || !c5 || !sigma_cex || !I_B0 || !j_ion || !div_angle)
-        return fail(PEM_ERR_INVALID_ARG, "pem_plume: NULL array");
-    if ((T == nullptr) != (T_c == nullptr)) return fail(PEM_ERR_INVALID_ARG, "pem_plume: T and T_c go together");
-    if (int rc = check_device()) return rc;
-    if (int rc = use_default_device()) return rc;
-    std::lock_guard<std::mutex> lock(g_ws.mu);
-    const size_t R = (size_t)n_radii;
-    // bound the profile chunk to ~256 MiB of device memory
-    size_t chunk = (size_t(1) << 28) / (NANG * R * 8);
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) & ~size_t(63);
-    const size_t need = 10 * padded(chunk * 8) + padded(chunk * NANG * R * 8) + 2 * padded(chunk * R * 8) + padded(chunk);
-    if (int rc = g_ws.reserve(need)) return rc;
-    unsigned char* const base = host_call_base(need);
-    const double* in[10] = {P_b, c0, c1, c2, c3, c4, c5, sigma_cex, I_B0, T};
-    for (size_t off = 0; off < n; off += chunk) {
-        const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[10];
-        for (auto& p : d) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        double* dj = cv.take<double>(chunk * NANG * R);
-        double* ddiv = cv.take<double>(chunk * R);
-        double* dtc = cv.take<double>(chunk * R);
-        uint8_t* dinv = cv.take<uint8_t>(chunk);
-        Mover mv(base, in_end, cv.off);
-        for (int i = 0; i < 10; ++i)
-            if (in[i]) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
-        PEM_TRY(mv.flush_in());
-        if (int rc = pem_plume_f64_dev(m, n_radii, radii, torr2pa, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8],
-                                       T ? d[9] : nullptr, dj, ddiv, T ? dtc : nullptr, invalid ? dinv : nullptr, nullptr))
-            return rc;
-        PEM_TRY(mv.out(j_ion + off * NANG * R, dj, m * NANG * R * 8));
-        PEM_TRY(mv.out(div_angle + off * R, ddiv, m * R * 8));
-        if (T) PEM_TRY(mv.out(T_c + off * R, dtc, m * R * 8));
-        if (invalid) PEM_TRY(mv.out(invalid + off, dinv, m));
-        PEM_TRY(mv.finish());
-    }
-    return PEM_OK;
-}
-
-int pem_coupled_f64(size_t n, double torr2pa, double radius, const double* P_b, const double* V_a, const double* T_e,
-                    const double* V_vac, const double* Pstar, const double* P_T, const double* mdot_a, const double* a_1,
-                    const double* c0, const double* c1, const double* c2, const double* c3, const double* c4,
-                    const double* c5, const double* sigma_cex, double* V_cc, double* I_B0, double* T, double* j_ion,
-                    double* div_angle, double* T_c, uint8_t* invalid) {
-    if (n == 0) return PEM_OK;
-    const double* in[15] = {P_b, V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, c0, c1, c2, c3, c4, c5, sigma_cex};
-    for (auto p : in)
-        if (!p) return fail(PEM_ERR_INVALID_ARG, "pem_coupled: NULL input array");
-    if (!V_cc || !div_angle || !T_c) return fail(PEM_ERR_INVALID_ARG, "pem_coupled: NULL output array");
-    if (int rc = check_device()) return rc;
-    if (int rc = use_default_device()) return rc;
-    std::lock_guard<std::mutex> lock(g_ws.mu);
-    size_t chunk = (size_t(1) << 28) / (NANG * 8);
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) & ~size_t(63);
-    const size_t need = 20 * padded(chunk * 8) + padded(chunk * NANG * 8) + padded(chunk);
-    if (int rc = g_ws.reserve(need)) return rc;
-    unsigned char* const base = host_call_base(need);
-    for (size_t off = 0; off < n; off += chunk) {
-        const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[15];
-        for (auto& p : d) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        double* dvcc = cv.take<double>(chunk);
-        double* dib0 = cv.take<double>(chunk);
-        double* dT = cv.take<double>(chunk);
-        double* ddiv = cv.take<double>(chunk);
-        double* dtc = cv.take<double>(chunk);
-        uint8_t* dinv = cv.take<uint8_t>(chunk);
-        double* dj = cv.take<double>(chunk * NANG);   // last: without a profile the staged copy-back stops before it
-        Mover mv(base, in_end, cv.off);
-        for (int i = 0; i < 15; ++i) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
-        PEM_TRY(mv.flush_in());
-        if (int rc = pem_coupled_f64_dev(m, torr2pa, radius, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9],
-                                         d[10], d[11], d[12], d[13], d[14], dvcc, I_B0 ? dib0 : nullptr, T ? dT : nullptr,
-                                         j_ion ? dj : nullptr, ddiv, dtc, invalid ? dinv : nullptr, nullptr))
-            return rc;
-        PEM_TRY(mv.out(V_cc + off, dvcc, m * 8));
-        if (I_B0) PEM_TRY(mv.out(I_B0 + off, dib0, m * 8));
-        if (T) PEM_TRY(mv.out(T + off, dT, m * 8));
-        if (j_ion) PEM_TRY(mv.out(j_ion + off * NANG, dj, m * NANG * 8));
-        PEM_TRY(mv.out(div_angle + off, ddiv, m * 8));
-        PEM_TRY(mv.out(T_c + off, dtc, m * 8));
-        if (invalid) PEM_TRY(mv.out(invalid + off, dinv, m));
-        PEM_TRY(mv.finish());
-    }
-    return PEM_OK;
 }
 
 }  // extern "C"
