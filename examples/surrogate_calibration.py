@@ -11,7 +11,11 @@ the same calibration through the true model, on one MI355X.
 With the analytic thruster test double the model is far cheaper than its surrogate: the point of the surrogate route is a plugged-in
 solver that costs seconds per sample.
 
-    python examples/surrogate_calibration.py [refinement iterations]          (default 60)
+    python examples/surrogate_calibration.py [refinement iterations] [--uion]          (default 60)
+
+--uion: the thruster surrogate also carries the ion velocity profile (its SVD latents, `fit(targets=(..., 'u_ion'))`), the data gain
+ion velocities at measured axial positions -- all four quantities of the reference's `System` calibration, one
+`pem_chain_fields_loglik_f64_dev` per evaluation -- and the replay through the surrogate is timed with and without them.
 """
 import sys
 import time
@@ -29,7 +33,9 @@ from hallthrusterpem_amd.optimize import DifferentialEvolution                  
 from hallthrusterpem_amd.sampling import NORMAL, PEM_V0_PRIORS, Prior                        # noqa: E402
 from hallthrusterpem_amd.system import PemV0System                                           # noqa: E402
 
-n_iter = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+UION = '--uion' in sys.argv[1:]
+args = [v for v in sys.argv[1:] if v != '--uion']
+n_iter = int(args[0]) if args else 60
 NAMES = ('T_e', 'V_vac', 'c0', 'c3')
 STAR = {'T_e': 3.0, 'V_vac': 30.0, 'c0': 0.35, 'c3': 0.6}
 FIXED = {'Pstar': 5e-5, 'P_T': 5e-5, 'c1': 0.3, 'c2': 5.0, 'c4': 1e20, 'c5': 1e16, 'sigma_cex': 55e-20}
@@ -40,9 +46,11 @@ system = PemV0System(seed=0)
 xt = system.sample_inputs(2000, normalize=False)
 xt.update({k: np.full(2000, v) for k, v in FIXED.items()})
 yt = system.predict(xt, use_model='best', normalized_inputs=False)
+if UION:
+    yt['u_ion'] = thruster_analytic({'V_a': xt['V_a'], 'V_cc': yt['V_cc'], 'mdot_a': xt['mdot_a'], 'a_1': xt['a_1']}, num_cells=200)['u_ion']
 t0 = time.perf_counter()
-hist = system.fit(targets=['V_cc', 'div_angle', 'T_c', 'j_ion'], fixed=FIXED, max_iter=n_iter, max_tol=0.0, num_refine=1000,
-                  test_set=(xt, yt), components=True)
+hist = system.fit(targets=['V_cc', 'div_angle', 'T_c', 'j_ion'] + (['u_ion'] if UION else []), fixed=FIXED, max_iter=n_iter, max_tol=0.0,
+                  num_refine=1000, test_set=(xt, yt), components=True)
 surr = system.surrogate
 print(f'fit(components=True): {len(hist)} iterations in {time.perf_counter() - t0:.1f} s, evaluations per component {surr.model_evals}, '
       f'j_ion rank {surr.compression.rank}')
@@ -59,7 +67,7 @@ def model(o):
     x = {k: np.full(o.shape[0], v) for k, v in {**FIXED, **STAR, 'a_1': A_1}.items()}
     x.update({k: o[:, j] for j, k in enumerate(OPERATING)})
     out = pem_v0_coupled(x)
-    th = thruster_analytic({'V_a': x['V_a'], 'V_cc': out['V_cc'], 'mdot_a': x['mdot_a'], 'a_1': x['a_1']})
+    th = thruster_analytic({'V_a': x['V_a'], 'V_cc': out['V_cc'], 'mdot_a': x['mdot_a'], 'a_1': x['a_1']}, num_cells=200 if UION else None)
     return out, th
 
 
@@ -71,6 +79,13 @@ data['T'] = {'x': ops['T'], 'y': np.asarray(th['T']), 'var_y': (0.02 * np.asarra
 out, _ = model(ops['jion'])
 j = np.stack([np.interp(np.abs(alpha), grid, np.asarray(out['j_ion'])[e]) for e in range(5)])
 data['jion'] = {'x': ops['jion'], 'y': j, 'var_y': (0.05 * j + 1e-3) ** 2, 'loc': np.stack([np.ones(alpha.size), alpha], 1)}
+lik_few = SystemLikelihood(data)
+if UION:                                                         # ion velocities at 20 axial positions of 4 more conditions
+    ops['uion'] = op(4)
+    zloc = np.linspace(0.002, 0.078, 20)
+    _, th = model(ops['uion'])
+    u = np.stack([np.interp(zloc, np.asarray(th['u_ion_coords']), np.asarray(th['u_ion'])[e]) for e in range(4)])
+    data['uion'] = {'x': ops['uion'], 'y': u, 'var_y': (0.05 * u + 100.0) ** 2, 'loc': zloc}
 lik = SystemLikelihood(data)
 
 # 3. the MAP through the surrogate and through the model: the model's posterior pins what the surrogate holds fixed
@@ -101,6 +116,9 @@ print(f'  {"":>6} {"surrogate":>12} {"model":>12} {"theta*":>12}')
 for i, k in enumerate(NAMES):
     print(f'  {k:>6} {res["surrogate"].theta[i]:12.5g} {res["model"].theta[i]:12.5g} {STAR[k]:12.5g}')
 # one graph replay of each posterior at the population's size, interleaved
+if UION:                                                         # the same surrogate on the data without the ion velocities
+    routes['surrogate, no u_ion data'] = lambda K: SurrogatePosterior(NAMES, lik_few, surr, n_chains=K, n_nuisance=M, seed=1,
+                                                                      fresh_nuisance=False, shared_nuisance=True)
 posts = {name: make(res['model'].theta.size * 15) for name, make in routes.items()}
 replays = {name: p.capture() for name, p in posts.items()}
 theta = torch.from_numpy(np.broadcast_to(res['model'].theta, (posts['model'].K, len(NAMES))).copy()).to(posts['model'].device)

@@ -260,17 +260,18 @@ class SurrogateInputMap:
         return t
 
 
-def surrogate_input_map(theta_names, operating, varied, fixed, priors, qois=(), field: bool = True):
+def surrogate_input_map(theta_names, operating, varied, fixed, priors, qois=(), field: bool = True, uion: bool = False):
     """The input map of a posterior evaluated through a chained surrogate (`chain.ChainedSurrogate`: its `varied`, `fixed`,
-    `priors`, whether it carries the j_ion latents) for the calibrated `theta_names`, the (Ne, 3) `operating` rows of P_b, V_a,
-    mdot_a and the measured `qois`.  Runs without a device.  ValueError for what the surrogate cannot serve."""
+    `priors`, whether it carries the j_ion latents (`field`) and the u_ion latents (`uion`)) for the calibrated `theta_names`, the
+    (Ne, 3) `operating` rows of P_b, V_a, mdot_a and the measured `qois`.  Runs without a device.  ValueError for what the
+    surrogate cannot serve."""
     varied, fixed = tuple(varied), dict(fixed)
     for k in theta_names:
         if k in fixed:
             raise ValueError(f"'{k}' cannot be calibrated: the surrogate holds it fixed at {fixed[k]}")
         if k not in varied:
             raise ValueError(f"'{k}' cannot be calibrated: the surrogate does not know it (its varied inputs are {varied})")
-    if 'uion' in qois:
+    if 'uion' in qois and not uion:
         raise ValueError("the likelihood holds 'uion' records: the chain carries no u_ion latents yet (the thruster stage predicts "
                          "I_B0 and T only)")
     if 'jion' in qois and not field:
@@ -313,13 +314,16 @@ class SurrogatePosterior(BatchedPosterior):
         evaluation: the physical inputs assembled as in `BatchedPosterior`, the surrogate's rows mapped to coordinates on the
         device, ONE `pem_chain_system_loglik_f64_dev` (chain, j_ion nodes, Gaussian sums and the discharge term from the
         surrogate's I_B0), then `pem_loglik_marginal_f64_dev` without a discharge term of its own.  `likelihood` may hold V_cc, T
-        and jion records; uion is refused (`surrogate_input_map`)."""
+        and jion records, and uion records when the surrogate was built with `u_ion` (the launch is then
+        `pem_chain_fields_loglik_f64_dev`: all four quantities of `QOI_MAP['System']`); otherwise uion is refused
+        (`surrogate_input_map`)."""
         import torch
         if not likelihood.use_discharge:
             discharge = None
         self.surrogate = surrogate
         self.map = surrogate_input_map(theta_names, likelihood.operating, surrogate.varied, surrogate.fixed, surrogate.priors,
-                                       likelihood.qois, field=surrogate.field is not None)
+                                       likelihood.qois, field=surrogate.field is not None,
+                                       uion=getattr(surrogate, 'u_compression', None) is not None)
         if likelihood.device != surrogate.device:
             raise ValueError(f'the likelihood lives on {likelihood.device}, the surrogate on {surrogate.device}')
         self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, surrogate.priors, seed, None,

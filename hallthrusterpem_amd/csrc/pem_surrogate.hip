@@ -595,8 +595,40 @@ void launch_chain_loglik(size_t n, int n_dim, int vcc_slot, int ib0_slot, const 
                        ib0_slot, s[0], s[1], s[2], map[0], map[1], map[2], map[3], t, ld, basis_words, lk);
 }
 
+// what both chained entry points ask of the slots, the coupling domains and the three tables; fills the kernels' view of the stages
+// and the largest stage's outer-basis words per thread
+int check_chain(const char* who, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
+                double ib0_lo, double ib0_w, ChainStage (&cs)[3], int& basis_words, int thr_out = 2) {
+    if (!stages) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL stage array", who);
+    if (n_dim < 2 || n_dim > PEM_SURR_MAX_DIM)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: 2 <= n_dim <= %d (the external coordinates and the two coupling slots)", who, PEM_SURR_MAX_DIM);
+    if (vcc_slot < 0 || vcc_slot >= n_dim || ib0_slot < 0 || ib0_slot >= n_dim || vcc_slot == ib0_slot)
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the V_cc and I_B0 slots are two different coordinates < n_dim", who);
+    if (!std::isfinite(vcc_lo) || !std::isfinite(vcc_w) || !(vcc_w > 0.0) || !std::isfinite(ib0_lo) || !std::isfinite(ib0_w) || !(ib0_w > 0.0))
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: a coupling domain needs a finite lo and a finite width w > 0", who);
+    const int need_out[3] = {1, thr_out, 0};           // cathode: V_cc; thruster: I_B0, T [, u_ion latents]; plume: div_angle [, latents]
+    basis_words = 0;
+    for (int k = 0; k < 3; ++k) {
+        const pem_surr_stage& g = stages[k];
+        if (!g.index || !g.coef || !g.values) return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: NULL table", who, k);
+        if (g.n_beta < 1 || g.n_out < 1 || g.n_out > 16 || (need_out[k] && g.n_out != need_out[k]))
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: need n_beta >= 1 and n_out %s", who, k,
+                             k == 0 ? "== 1" : (k == 1 ? (thr_out == 2 ? "== 2" : "== 2 + u_rank") : "in 1 .. 16"));
+        if (g.max_active < 0 || g.max_active > PEM_SURR_MAX_ACTIVE || g.max_level < 0 || g.max_level > PEM_SURR_MAX_LEVEL)
+            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: at most %d active dimensions of level <= %d per multi-index", who, k,
+                             PEM_SURR_MAX_ACTIVE, PEM_SURR_MAX_LEVEL);
+        cs[k] = ChainStage{g.index, g.coef, g.values, g.n_beta, g.n_out, g.max_active > 1 ? g.max_active - 1 : 0,
+                           g.max_level == 0 ? 1 : (1 << g.max_level) + 1};
+        if (cs[k].max_outer * cs[k].max_m > basis_words) basis_words = cs[k].max_outer * cs[k].max_m;
+    }
+    return PEM_OK;
+}
+
 }  // namespace
 
+// pem_surrogate_fields.hip compiles this file's device code a second time (the node tables above stay in ONE place) and instantiates
+// its own kernels only: the entry points below, and with them every kernel instantiation of this file, are left out of that unit
+#ifndef PEM_SURROGATE_FIELDS_UNIT
 namespace {
 
 int sparse_predict(const char* who, size_t n, int n_dim, int n_beta, const int32_t* index, const double* coef, const double* values,
@@ -633,35 +665,6 @@ int sparse_predict(const char* who, size_t n, int n_dim, int n_beta, const int32
     }
 #undef PEM_PREDICT
     HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-// what both chained entry points ask of the slots, the coupling domains and the three tables; fills the kernels' view of the stages
-// and the largest stage's outer-basis words per thread
-int check_chain(const char* who, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo, double vcc_w,
-                double ib0_lo, double ib0_w, ChainStage (&cs)[3], int& basis_words) {
-    if (!stages) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL stage array", who);
-    if (n_dim < 2 || n_dim > PEM_SURR_MAX_DIM)
-        return pem::fail(PEM_ERR_INVALID_ARG, "%s: 2 <= n_dim <= %d (the external coordinates and the two coupling slots)", who, PEM_SURR_MAX_DIM);
-    if (vcc_slot < 0 || vcc_slot >= n_dim || ib0_slot < 0 || ib0_slot >= n_dim || vcc_slot == ib0_slot)
-        return pem::fail(PEM_ERR_INVALID_ARG, "%s: the V_cc and I_B0 slots are two different coordinates < n_dim", who);
-    if (!std::isfinite(vcc_lo) || !std::isfinite(vcc_w) || !(vcc_w > 0.0) || !std::isfinite(ib0_lo) || !std::isfinite(ib0_w) || !(ib0_w > 0.0))
-        return pem::fail(PEM_ERR_INVALID_ARG, "%s: a coupling domain needs a finite lo and a finite width w > 0", who);
-    static const int need_out[3] = {1, 2, 0};          // cathode: V_cc; thruster: I_B0, T; plume: div_angle [, latents]
-    basis_words = 0;
-    for (int k = 0; k < 3; ++k) {
-        const pem_surr_stage& g = stages[k];
-        if (!g.index || !g.coef || !g.values) return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: NULL table", who, k);
-        if (g.n_beta < 1 || g.n_out < 1 || g.n_out > 16 || (need_out[k] && g.n_out != need_out[k]))
-            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: need n_beta >= 1 and n_out %s", who, k,
-                             k == 0 ? "== 1" : (k == 1 ? "== 2" : "in 1 .. 16"));
-        if (g.max_active < 0 || g.max_active > PEM_SURR_MAX_ACTIVE || g.max_level < 0 || g.max_level > PEM_SURR_MAX_LEVEL)
-            return pem::fail(PEM_ERR_INVALID_ARG, "%s: stage %d: at most %d active dimensions of level <= %d per multi-index", who, k,
-                             PEM_SURR_MAX_ACTIVE, PEM_SURR_MAX_LEVEL);
-        cs[k] = ChainStage{g.index, g.coef, g.values, g.n_beta, g.n_out, g.max_active > 1 ? g.max_active - 1 : 0,
-                           g.max_level == 0 ? 1 : (1 << g.max_level) + 1};
-        if (cs[k].max_outer * cs[k].max_m > basis_words) basis_words = cs[k].max_outer * cs[k].max_m;
-    }
     return PEM_OK;
 }
 
@@ -833,3 +836,4 @@ int pem_chain_system_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_s
 }
 
 }  // extern "C"
+#endif  // PEM_SURROGATE_FIELDS_UNIT

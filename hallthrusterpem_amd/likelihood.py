@@ -162,7 +162,8 @@ class SystemLikelihood:
         self.n_rec, self.n_node = n_rec, len(node)
         self.rec = f(np.concatenate(blocks))
         self.span = f(span)
-        self.node = f(np.asarray(node if node else [0, 0], dtype=np.int32))
+        self.node_host = np.asarray(node if node else [0, 0], dtype=np.int32)      # (an entry point that checks the table reads this copy)
+        self.node = f(self.node_host)
         self.data = {q: data[q] for q in qois}
 
     def _check(self, q, d):

@@ -253,12 +253,18 @@ class PemV0System:
             out[s.field] = f.reshape(shape + (f.shape[-1],))
             from .models.plume import _coords, angle_grid
             out[f'{s.field}{COORDS_STR_ID}'] = _coords(shape, angle_grid())
+        if 'u_ion' in y:                                     # the thruster carries the ion velocity profile (fit(targets=(.., 'u_ion')))
+            from .models.plume import _coords
+            u = y['u_ion'].cpu().numpy()
+            out['u_ion'] = u.reshape(shape + (u.shape[-1],))
+            out[f'u_ion{COORDS_STR_ID}'] = _coords(shape, y['u_ion_coords'].cpu().numpy())
         return out
 
     def _test_error(self, qoi, test_set):
         xt, yt = test_set
         pred = self._predict_surrogate(xt)
-        # relative L2 error per target (fit_surr.py:121-133 plots exactly this); a log10-normalised field in its norm
+        # relative L2 error per target (fit_surr.py:121-133 plots exactly this); a log10-normalised field in its norm (u_ion's
+        # linear norm is a constant factor: it cancels)
         nrm = lambda k, v: np.log10(np.asarray(v, dtype=np.float64)) if k == 'j_ion' else np.asarray(v, dtype=np.float64)   # noqa: E731
         return {k: float(np.linalg.norm(nrm(k, pred[k]) - nrm(k, yt[k])) / np.linalg.norm(nrm(k, yt[k]))) for k in qoi if k in yt}
 
@@ -269,14 +275,21 @@ class PemV0System:
     def _fit_components(self, qoi, varied, fixed, max_iter, max_tol, num_refine, seed, test_set):
         """fit(components=True): one surrogate per component, cost-weighted greedy allocation (chain.py)"""
         from .chain import COST_SHARES, ChainedSurrogate
-        field = 'j_ion' in qoi
+        field, uion = 'j_ion' in qoi, 'u_ion' in qoi
         s = self.surrogate
         if not self._chained() or s.varied != tuple(k for k in COUPLED_INPUTS if k in set(varied)) or s.fixed != fixed \
-                or bool(s.field) != field:
+                or bool(s.field) != field or (s.u_compression is not None) != uion:
             comp = None
             if field and self._outputs['j_ion'].compression is not None and self._outputs['j_ion'].compression.svd.basis is not None:
                 comp = self._outputs['j_ion'].compression.svd
-            self.surrogate = ChainedSurrogate(varied, fixed=fixed, priors=self.priors, field=field, compression=comp, seed=seed)
+            ucomp = False
+            if uion:                                         # process_compression's u_ion map when it has run, else one fitted for the box
+                ucomp = True
+                if 'u_ion' in self._outputs and self._outputs['u_ion'].compression is not None \
+                        and self._outputs['u_ion'].compression.svd.basis is not None:
+                    ucomp = self._outputs['u_ion'].compression.svd
+            self.surrogate = ChainedSurrogate(varied, fixed=fixed, priors=self.priors, field=field, compression=comp, seed=seed,
+                                              u_ion=ucomp)
             self.train_history = []
         self._set_costs(COST_SHARES)
         s = self.surrogate
@@ -303,7 +316,8 @@ class PemV0System:
         target]) is appended to `train_history`.
 
         components=True: one surrogate per component (cathode, thruster, plume) chained through V_cc and I_B0, as the reference
-        trains them (chain.py).  `targets` picks the test errors and whether the plume carries j_ion; each history entry also
+        trains them (chain.py).  `targets` picks the test errors, whether the plume carries j_ion and -- with 'u_ion' -- whether the
+        thruster carries the ion velocity profile; each history entry also
         names its `component` and the per-component cumulative `component_evals`, and `model_evals` is cost-weighted by the
         components' `model_costs` (their kernels' bytes per evaluation, summing to 1)."""
         from .surrogate import SparseGridSurrogate

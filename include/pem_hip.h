@@ -417,6 +417,50 @@ int pem_chain_system_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_s
                                     const int32_t* span, const double* a_1, double discharge_current, double discharge_sigma,
                                     double* loglik, double* out, size_t ld_out, double* pred, size_t ld_pred, pem_stream_t stream);
 
+/* The two chained launches with the ion velocity carried through the thruster stage (scripts/pem_v0/pem_v0_SPT-100.yml:207-214: `u_ion`
+ * is compressed as `j_ion` is -- svd, reconstruction_tol 0.01 -- under norm linear(1.0e-3); train-shim.sh:9-11 trains it with the thruster
+ * component; mcmc.py:88-89 reconstructs it inside the likelihood).  Arguments as the parents', then the thruster stage's field:
+ *   u_lat0 (== 2), u_rank (0 .. 14): the thruster table has n_out == 2 + u_rank outputs I_B0, T, l_0 .. l_{u_rank-1}
+ *   u_dof (>= 2): the cells of the u_ion grid; u_norm / u_scale / u_basis[u_dof][u_rank]: as pem_svd_reconstruct_f64_dev
+ *   u[c] = denorm(v), v = 0; v = fma(l_q, u_basis[c][q], v), q = 0 .. u_rank - 1 (pem_sparse_predict_field_f64_dev's expression;
+ *          PEM_NORM_LINEAR: v / u_scale)
+ * pem_sparse_predict_chain_fields_f64_dev: out has u_rank more rows, [4 + n_out(plume) + u_rank][ld_out]: the parent's, then l_0 ...;
+ *   u_field (NULL or [n][u_dof]): u[c] of every cell.
+ * pem_chain_fields_loglik_f64_dev: out (optional) as above.  node ([n_node] int32 DEVICE array) and node_host (the caller's HOST copy
+ *   of it, the one that is checked: every entry in [0, u_dof); the kernel clamps the device entries into the grid, so a copy that
+ *   differs reads no memory outside u_basis): likelihood.SystemLikelihood's table of pem_coupled_system_loglik_f64_dev.  n_node is 0
+ *   (no u_ion records) or 2 .. 2 PEM_FUSED_SYSTEM_MAX_RECORDS; the spans live in device memory, so u_ion records that meet n_node == 0
+ *   cannot be refused: their condition gets NaN.
+ *   PEM_SYS_UION  {w, y, 1/std, p}  m = fma(w, u[b] - u[a], u[a]), a = node[p], b = node[p + 1], p clamped to n_node - 2 as
+ *                                   pem_coupled_system_loglik_f64_dev clamps it
+ *   loglik[i]: the terms in the order u_ion, j_ion, V_cc, T (each kind in record order), then the discharge term, every one added by
+ *   one fma(-0.5 z, z, sum) from 0.  The u_ion terms and u_field are evaluated between the thruster and the plume stage.
+ * Bit contracts (tests/test_chain_uion.py):
+ *   1. u_rank == 0: the parents' kernels run; every output equals the parent entry point's bit for bit, u_ion records give NaN and
+ *      the other u_* / node arguments are not looked at (n_node's range aside).
+ *   2. u_rank > 0: V_cc, I_B0, T, div_angle, T_c, the plume's outputs, the j_ion field and the loglik / pred of every condition
+ *      without u_ion records equal, bit for bit, what the parent returns for the same chain with the thruster table cut to its first
+ *      two value columns (a column of a stage is summed independently of the others).
+ *   3. A sample's loglik, pred and u_field bits depend on its coordinates, its condition and the tables only -- not on n, its
+ *      position, the grid, whether the tables were staged in LDS or which optional outputs are asked for.
+ * LDS: the parent's policy; the u_ion latents take basis slots of their thread (counted), and of u_basis only the n_node rows the node
+ * table names are gathered, once per workgroup, beside the record table where that is staged.  Every argument is checked before the
+ * device is: NULL u_basis with u_rank > 0, u_lat0 != 2, u_dof < 2, an unknown u_norm, a zero or non-finite u_scale under
+ * PEM_NORM_LINEAR, stages[1].n_out != 2 + u_rank, n_node outside
+ * its range or == 1, a NULL node / node_host with n_node > 0, a node_host entry outside [0, u_dof). */
+int pem_sparse_predict_chain_fields_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                            double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, double* out, size_t ld_out,
+                                            int lat0, int rank, int dof, int norm, double norm_scale, const double* basis, double* field,
+                                            int u_lat0, int u_rank, int u_dof, int u_norm, double u_scale, const double* u_basis,
+                                            double* u_field, pem_stream_t stream);
+int pem_chain_fields_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_slot, const pem_surr_stage* stages, double vcc_lo,
+                                    double vcc_w, double ib0_lo, double ib0_w, const double* t, size_t ld, int lat0, int rank, int dof,
+                                    int norm, double norm_scale, const double* basis, int n_cond, int n_rec, const double* rec,
+                                    const int32_t* span, const double* a_1, double discharge_current, double discharge_sigma,
+                                    double* loglik, double* out, size_t ld_out, double* pred, size_t ld_pred, int u_lat0, int u_rank,
+                                    int u_dof, int u_norm, double u_scale, const double* u_basis, int n_node, const int32_t* node,
+                                    const int32_t* node_host, pem_stream_t stream);
+
 /* ---- per-column order statistics over the sample axis -------------------------------------------------------------
  * The percentiles of scripts/gen_data.py:125-174 (`np.percentile(arr, 25 | 75, axis=0)`, NaN / interquartile-range masks) and
  * of scripts/pem_v0/monte_carlo.py:363-658 (5 / 50 / 95 % bands) at forward-UQ sizes, by exact radix selection instead of a
