@@ -6,7 +6,7 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
-SRCS = [PKG / 'csrc' / 'pem_kernels.hip', PKG / 'csrc' / 'pem_radii.hip', PKG / 'csrc' / 'pem_stages.hip', PKG / 'csrc' / 'pem_host.hip', PKG / 'csrc' / 'pem_campaign.hip', PKG / 'csrc' / 'pem_sampler.hip', PKG / 'csrc' / 'pem_svd.hip', PKG / 'csrc' / 'pem_likelihood.hip', PKG / 'csrc' / 'pem_surrogate.hip', PKG / 'csrc' / 'pem_surrogate_fields.hip', PKG / 'csrc' / 'pem_fp32.hip', PKG / 'csrc' / 'pem_saltelli.hip', PKG / 'csrc' / 'pem_latent.hip', PKG / 'csrc' / 'pem_quantile.hip', PKG / 'csrc' / 'pem_masks.hip', PKG / 'csrc' / 'pem_sobol_sweep.hip', PKG / 'csrc' / 'pem_de.hip', PKG / 'csrc' / 'pem_chains.hip', PKG / 'csrc' / 'pem_marginals.hip']
+SRCS = [PKG / 'csrc' / 'pem_kernels.hip', PKG / 'csrc' / 'pem_radii.hip', PKG / 'csrc' / 'pem_stages.hip', PKG / 'csrc' / 'pem_host.hip', PKG / 'csrc' / 'pem_campaign.hip', PKG / 'csrc' / 'pem_sampler.hip', PKG / 'csrc' / 'pem_svd.hip', PKG / 'csrc' / 'pem_likelihood.hip', PKG / 'csrc' / 'pem_surrogate.hip', PKG / 'csrc' / 'pem_surrogate_fields.hip', PKG / 'csrc' / 'pem_surrogate_sobol.hip', PKG / 'csrc' / 'pem_fp32.hip', PKG / 'csrc' / 'pem_saltelli.hip', PKG / 'csrc' / 'pem_latent.hip', PKG / 'csrc' / 'pem_quantile.hip', PKG / 'csrc' / 'pem_masks.hip', PKG / 'csrc' / 'pem_sobol_sweep.hip', PKG / 'csrc' / 'pem_de.hip', PKG / 'csrc' / 'pem_chains.hip', PKG / 'csrc' / 'pem_marginals.hip']
 LIB = PKG / 'libpem_hip.so'
 DEPS = SRCS + sorted((PKG / 'csrc').glob('*.h')) + [ROOT / 'include' / 'pem_hip.h']
 
@@ -44,12 +44,14 @@ def needs_build() -> bool:
 
 def _object_hash(src: Path, flags) -> str:
     """Digest of everything one object file depends on: its source (and a unit it includes whole, as pem_surrogate_fields.hip
-    includes pem_surrogate.hip), every header, the flags."""
+    includes pem_surrogate.hip, followed through every level), every header, the flags."""
     import hashlib
     import re
     h = hashlib.sha256()
     h.update(' '.join(flags).encode())
-    units = [src] + [src.parent / m for m in re.findall(r'^#include "(\w+\.hip)"', src.read_text(), re.M)]
+    units = [src]
+    for u in units:                                   # (a unit may include a unit that includes one: pem_surrogate_sobol.hip)
+        units += [u.parent / m for m in re.findall(r'^#include "(\w+\.hip)"', u.read_text(), re.M)]
     for d in units + [d for d in DEPS if d.suffix == '.h']:
         h.update(d.name.encode())
         h.update(d.read_bytes())

@@ -280,6 +280,13 @@ int check_uion(const char* who, int u_lat0, int u_rank, int u_dof, int u_norm, d
     return PEM_OK;
 }
 
+}  // namespace
+
+// pem_surrogate_sobol.hip compiles this file's device code once more, as this file compiles pem_surrogate.hip's: the entry points
+// below, and with them every kernel instantiation of this file, are left out of that unit
+#ifndef PEM_SURROGATE_SOBOL_UNIT
+namespace {
+
 // Instantiations: thruster width 3 exact (the test double's profile is v_exh s(z): exactly rank 1) and 16 guarded (a plugged-in
 // solver's 2 .. 14 latents); plume widths 1 exact (no j_ion), 8 and 16 guarded.  A stage's columns are summed independently of each
 // other, so the width of an instantiation changes no bit of any output.
@@ -435,3 +442,4 @@ int pem_chain_fields_loglik_f64_dev(size_t n, int n_dim, int vcc_slot, int ib0_s
 }
 
 }  // extern "C"
+#endif  // PEM_SURROGATE_SOBOL_UNIT

@@ -7,6 +7,8 @@ These follow the SHAPE of the reference's drivers
                       own `_filter_outputs` results, extracted and run by tests/golden/make_golden.py)
   * `forward_uq`      scripts/pem_v0/monte_carlo.py:63-300  (Ns samples -> predict -> statistics)
   * `sobol_indices`   scripts/pem_v0/sobol.py:46-118  first-order + total indices (compute_s2=False)
+  * `sobol_sweep`     the same study per QoI group over a sweep of background pressures, around the model or, with
+                      `surrogate=`, around a trained `chain.ChainedSurrogate` as sobol.py:70-98 evaluates it
 The sampler / Sobol' estimator implementations of the reference are amisc / uqtils (third-party, absent): PARITY
 UNPINNED for those two; the estimators used here are stated in the docstrings.
 
@@ -734,7 +736,8 @@ def sample_plume_without_spikes(n: int, seed: int = 0, threshold: float = 200.0,
 
 # ------------------------------------------------------------------------------------------- Sobol' indices over a pressure sweep
 def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'), seed: int = 0, spike_threshold: float = 200.0,
-                clip_percentile: float | None = 99.0, l_ch: float = 0.025, uion_grid=None, max_attempts: int = 64, device=None):
+                clip_percentile: float | None = 99.0, l_ch: float = 0.025, uion_grid=None, max_attempts: int = 64, device=None,
+                surrogate=None):
     """First-order and total Sobol' indices, with standard errors, of V_cc, thrust T, ion velocity uion at z = l_ch and ion
     current density jion at gamma = 0 over a sweep of background pressures: the study of scripts/pem_v0/sobol.py:46-118.
 
@@ -745,8 +748,8 @@ def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'),
     pressure p, P_b is Relative(20) around p and mdot_a Relative(3) around 5e-6, READ AS uniform on nominal * (1 +- x / 100)
     intersected with the YAML domain (an assumption: amisc is absent); the calibration inputs keep their priors.
 
-    One fused fp64 launch per group covers every pressure (`pem_sobol_sweep_f64_dev`, csrc/pem_sobol_sweep.hip); only the
-    groups the requested QoIs need are launched.  Plume rows whose j_ion profile reaches `spike_threshold` anywhere are
+    One fused fp64 launch per group covers every pressure (`pem_sobol_sweep_f64_dev`, csrc/pem_sobol_sweep.hip, around the model;
+    `pem_chain_sobol_sweep_f64_dev` around a `surrogate`, see below); only the groups the requested QoIs need are launched.  Plume rows whose j_ion profile reaches `spike_threshold` anywhere are
     redrawn (at most `max_attempts` draws; a row never accepted raises), and with `clip_percentile` every jion evaluation at
     pressure p is clipped at thr_p, the percentile (numpy 'linear') of the accepted A and B rows' jion at p, found by a
     pre-pass of the same launch and `column_percentiles`.  uqtils clips each model call at its own percentile; one threshold
@@ -756,6 +759,15 @@ def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'),
         S1_i = mean(t1) / Var        ST_i = mean(t2) / (2 Var)
         se(S1_i) = sqrt((mean(t1^2) - mean(t1)^2) / N) / Var,   se(ST_i) the same of t2 over 2 Var.
     Single GPU, fp64 only: sharding over a process group and an fp32 model are not provided.
+
+    surrogate: a trained `chain.ChainedSurrogate` puts its cathode and thruster tables in the model's place for the Cathode and
+    Thruster groups, as the reference's model() takes V_cc, T and u_ion from `SURR.predict` (sobol.py:70-98): one
+    `pem_chain_sobol_sweep_f64_dev` launch per group (csrc/pem_surrogate_sobol.hip) on the SAME design rows as the model sweep of
+    that seed, mapped to the chain's coordinates, the plume stage never run.  uion is the cell of the chain's own grid nearest
+    l_ch (`uion_grid`, if given, must be the chain's); it needs a chain built with `u_ion`.  `sobol.surrogate_sweep_map` refuses
+    what the chain cannot serve.  The Plume group stays on the model (sobol.py:82-90): res['jion'] does not change.  The result
+    gains 'surrogate': True and 'extrapolated': the evaluations whose V_cc coupling coordinate left [-1, 1] (the thruster table
+    is extrapolated there).  surrogate=None: nothing changes.
 
     Returns {qoi: {'S1', 'ST', 'S1_se', 'ST_se': (P, d) float64 tensors, 'inputs': names, 'mean', 'var': (P,)}, 'P_b': (P,)
     numpy array, 'evaluations', 'non_physical', 'invalid': ints}; res['jion'] also carries 'clip' ((P,) tensor or None),
@@ -786,14 +798,27 @@ def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'),
         raise ValueError(f'clip_percentile must be in [0, 100] or None, got {clip_percentile}')
     if int(max_attempts) < 1:
         raise ValueError('max_attempts must be at least 1')
-    _, uion_z = study.uion_node(float(l_ch), UION_GRID if uion_grid is None else uion_grid)
+    if surrogate is not None and uion_grid is not None and (float(uion_grid[0]), float(uion_grid[1]), int(uion_grid[2])) != tuple(surrogate.uion_grid):
+        raise ValueError(f"uion_grid = {tuple(uion_grid)} is not the surrogate's {tuple(surrogate.uion_grid)}: the latents rebuild the profile "
+                         f'on the grid they were fitted on')
+    grid = surrogate.uion_grid if surrogate is not None else (UION_GRID if uion_grid is None else uion_grid)
+    uion_cell, uion_z = study.uion_node(float(l_ch), grid)
     groups = [g for g in study.GROUPS if any(study.QOI_GROUP[q] == g for q in qois)]
+    slot_maps = {}
+    if surrogate is not None:                                             # refusals come before any device work
+        has_u = getattr(surrogate, 'u_compression', None) is not None
+        slot_maps = {g: study.surrogate_sweep_map(surrogate.varied, surrogate.fixed, surrogate.priors, pb, g, has_u, qois)
+                     for g in groups if g in study.SURROGATE_GROUPS}
 
     lib = _lib.load()
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     n_p = pb.size
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                        # noqa: E731
     res = {'P_b': pb, 'evaluations': 0, 'non_physical': 0, 'invalid': 0}
+    if surrogate is not None:
+        if surrogate.device != dev:
+            raise ValueError(f'the surrogate lives on {surrogate.device}, the sweep runs on {dev}')
+        res.update(surrogate=True, extrapolated=0)
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
@@ -803,10 +828,19 @@ def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'),
             nv, nq = len(names), len(study.GROUP_QOIS[g])
             rows = 2 + 4 * nv
             kind, a, b = (torch.as_tensor(t, device=dev) for t in study.prior_tables(pb, g))
-            # workgroups resident at once over all pressures: 2 per CU for the Plume instantiation (256 registers), 4 otherwise
-            n_blocks = max(1, min(-(-n_base // 256), -(-cus * (2 if g == 'Plume' else 4) // n_p)))
+            sm = slot_maps.get(g)
+            if sm is not None:
+                # the chain's launch: as many workgroups as its LDS (the read stages' outer bases, the coordinates, 2.5 KB of
+                # accumulators) and its registers (up to 252: two per CU) keep resident
+                st, _keep = surrogate.stage_tables()
+                words = max((max(t.max_active - 1, 0)) * ((1 << t.max_level) + 1 if t.max_level else 1) for t in st[:2 if g == 'Thruster' else 1])
+                per_cu = max(1, min(2, (160 * 1024) // ((words + surrogate.n_dim) * 2048 + 2560)))
+                n_blocks = max(1, min(-(-n_base // 256), -(-cus * per_cu // n_p)))
+            else:
+                # workgroups resident at once over all pressures: 2 per CU for the Plume instantiation (256 registers), 4 otherwise
+                n_blocks = max(1, min(-(-n_base // 256), -(-cus * (2 if g == 'Plume' else 4) // n_p)))
             partial = torch.empty((n_p, n_blocks, rows, nq), dtype=torch.float64, device=dev)
-            flags = torch.empty((n_p, n_blocks, 4), dtype=torch.int64, device=dev)
+            flags = torch.empty((n_p, n_blocks, 4 if sm is None else 2), dtype=torch.int64, device=dev)
 
             def launch(clip, j0):
                 _lib.check(lib.pem_sobol_sweep_f64_dev(gid, n_base, 0, int(seed), n_p, ptr(kind), ptr(a), ptr(b), constants.TORR_2_PA,
@@ -817,9 +851,23 @@ def sobol_sweep(n_base: int, pressures=None, qois=('V_cc', 'T', 'uion', 'jion'),
                 j0 = torch.empty((n_p, 2 * n_base), dtype=torch.float64, device=dev)
                 launch(None, j0)
                 clip = column_percentiles(j0.T, float(clip_percentile)).contiguous()
-            launch(clip, None)
+            if sm is None:
+                launch(clip, None)
+            else:
+                cu = surrogate.u_compression
+                ubasis = cu.basis.contiguous() if cu is not None else None
+                vlo, vhi = surrogate.domains[0]
+                hp = lambda x: x.ctypes.data_as(C.c_void_p)                                     # noqa: E731
+                _lib.check(lib.pem_chain_sobol_sweep_f64_dev(
+                    gid, n_base, 0, int(seed), n_p, ptr(kind), ptr(a), ptr(b), surrogate.n_dim, surrogate.vcc_slot, surrogate.ib0_slot, st,
+                    vlo, vhi - vlo, hp(sm.rows), hp(sm.is_log), hp(sm.a), hp(sm.w), cu.rank if cu is not None else 0, int(grid[2]),
+                    cu.norm if cu is not None else 0, cu.scale if cu is not None else 1.0, ptr(ubasis), uion_cell, None, ptr(partial),
+                    ptr(flags), n_blocks, stream))
             s = partial.sum(dim=1)                                        # [P][rows][nq]
-            cnt = flags.sum(dim=1).cpu().numpy()                          # [P][4]
+            cnt = flags.sum(dim=1).cpu().numpy()                          # [P][4]; the chain's launch: [P][2]
+            if sm is not None:
+                res['extrapolated'] += int(cnt[:, 1].sum())
+                cnt = np.concatenate([cnt[:, :1], np.zeros((n_p, 3), dtype=cnt.dtype)], axis=1)
             if cnt[:, 3].any():
                 raise RuntimeError(f'{int(cnt[:, 3].sum())} plume rows still reach {spike_threshold} A/m^2 after {max_attempts} draws')
             mean = s[:, 0] / (2 * n_base)

@@ -14,7 +14,9 @@ scripts/pem_v0/monte_carlo.py.
 the predictions (`pem_coupled_system_predict_f64_dev`, JMODE 7 of the fused likelihood kernel: the j_ion profile stays in LDS),
 one column gather that drops the table's padding records, optionally the noise (`pem_predictive_noise_f64_dev`), and one
 `drivers.column_percentiles` over every column.  The reference's surrogate rows ("Surr-Data", "Surr-Model") and its discharge
-current check are not restated.  The reference's driver layer is stale and third-party: parity UNPINNED; the predictions are
+current check are not restated: of the reference's three analyses on its trained surrogate, the calibration
+(`calibration.SurrogatePosterior`) and the Sobol' study (`drivers.sobol_sweep(surrogate=)`) take a `chain.ChainedSurrogate`,
+this one runs the model only.  The reference's driver layer is stale and third-party: parity UNPINNED; the predictions are
 held to the oracle, the bands to numpy (tests/test_predictive.py).
 """
 import ctypes as C

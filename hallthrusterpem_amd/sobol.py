@@ -1,6 +1,8 @@
 """Definition of the Sobol' study of scripts/pem_v0/sobol.py:46-118 (`compute_indices`) over a sweep of background pressures:
 the nominal values of the 15 coupled inputs, the QoI groups and the inputs each varies, and the per-pressure prior tables.
-`drivers.sobol_sweep` runs the study (csrc/pem_sobol_sweep.hip).
+`drivers.sobol_sweep` runs the study (csrc/pem_sobol_sweep.hip), around the model or, for the Cathode and Thruster groups, around
+a trained `chain.ChainedSurrogate` (`surrogate_sweep_map`, csrc/pem_surrogate_sobol.hip) as the reference's model() does
+(sobol.py:70-98).
 
 Per QoI the reference varies only the exogenous inputs of the component that produces it (IDX_MAP, sobol.py:24-29); every
 other input sits at its nominal value (sobol.py:73-80) and `V_a` (with `r_m`) is held constant (CONSTANTS).  The groups:
@@ -102,3 +104,97 @@ def uion_node(l_ch: float, uion_grid):
 def row_stream(group: int, n_p: int, p: int, attempt: int, row: int) -> int:
     """Stream of attempt `attempt` of row `row` (0: A, 1: B) of group `group` at pressure index `p` (include/pem_hip.h)."""
     return 2 * len(GROUPS) * n_p * attempt + 2 * (group * n_p + p) + row
+
+
+# ---- the study through a chained surrogate (sobol.py:70-98: V_cc, T and u_ion come from SURR.predict) ---------------------------
+SURROGATE_GROUPS = ('Cathode', 'Thruster')                        # the Plume group stays on the model (sobol.py:82-90)
+# what each group's stages read: the cathode component's inputs, and for the Thruster group the thruster component's as well
+_CATHODE_READS = ('P_b', 'V_a', 'T_e', 'V_vac', 'Pstar', 'P_T')
+GROUP_READS = {'Cathode': _CATHODE_READS, 'Thruster': _CATHODE_READS + ('mdot_a', 'a_1')}
+
+
+class SweepSlotMap:
+    """How the rows of the study's design become the external coordinates of a chained surrogate: slot k reads input row
+    `rows[k]`, u = log10(x) where `is_log[k]`, t = 2.0 * (u - a[k]) / w[k] - 1.0 with w = b - a formed here in float64.  The
+    arrays are the slot table of `pem_chain_sobol_sweep_f64_dev`; `coords` is the numpy form of the map."""
+
+    def __init__(self, rows, is_log, a, w):
+        self.rows = np.ascontiguousarray(rows, dtype=np.int32)
+        self.is_log = np.ascontiguousarray(is_log, dtype=np.int32)
+        self.a = np.ascontiguousarray(a, dtype=np.float64)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+
+    def coords(self, x):
+        """x: (15, n) physical inputs -> (n_ext, n) coordinates, left to right as the kernel forms them"""
+        x = np.asarray(x, dtype=np.float64)
+        t = np.empty((len(self.rows), x.shape[1]))
+        for d, r in enumerate(self.rows):
+            u = np.log10(x[r]) if self.is_log[d] else x[r]
+            t[d] = 2.0 * (u - self.a[d]) / self.w[d] - 1.0
+        return t
+
+
+def _box_coordinate(prior: sampling.Prior, value: float) -> float:
+    """`value` in the units a surrogate's box [prior.a, prior.b] is stated in (log10 for a log-uniform input)"""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return float(np.log10(value)) if prior.kind == sampling.LOGUNIFORM else float(value)
+
+
+def surrogate_sweep_map(chain_varied, chain_fixed, chain_priors, pressures, group: str, has_uion: bool = False, qois=()):
+    """The slot table of the study's `group` at `pressures` evaluated through a chained surrogate (`chain.ChainedSurrogate`: its
+    `varied`, `fixed`, `priors` and whether it carries the u_ion latents).  Runs without a device.  ValueError, naming the input,
+    for what the surrogate cannot serve: a varied input of the group it does not vary, an input the group's stages read that it
+    fixes away from `PEM_V0_NOMINAL`, a pin or a sweep range outside its box, a normal prior, `uion` without latents.  Inputs
+    that only the plume stage reads are not examined (the launch never runs that stage)."""
+    if group not in SURROGATE_GROUPS:
+        raise ValueError(f'group {group!r}: a chained surrogate serves the groups {SURROGATE_GROUPS}; the Plume group stays on the model')
+    varied, fixed = tuple(k for k in COUPLED_INPUTS if k in set(chain_varied)), dict(chain_fixed)
+    if 'uion' in qois and not has_uion:
+        raise ValueError("'uion' is asked of a chain without u_ion latents (the thruster stage predicts I_B0 and T only): build it "
+                         'with u_ion=True')
+    tol = 8 * np.finfo(np.float64).eps
+    inside = lambda u, p: p.a - tol * abs(p.a) <= u <= p.b + tol * abs(p.b)                      # noqa: E731
+    sweeps = [sweep_priors(p, group) for p in np.atleast_1d(np.asarray(pressures, dtype=np.float64))]
+    for k in GROUP_READS[group]:
+        is_var = k in GROUP_INPUTS[group]
+        if k in fixed:
+            if is_var:
+                raise ValueError(f"'{k}' is varied by the {group} group and the surrogate holds it fixed at {fixed[k]}")
+            if float(fixed[k]) != PEM_V0_NOMINAL[k]:
+                raise ValueError(f"the surrogate holds '{k}' fixed at {fixed[k]}; the study pins it at its nominal value {PEM_V0_NOMINAL[k]}")
+            continue
+        if k not in varied:
+            raise ValueError(f"'{k}' is read by the {group} group and the surrogate neither varies nor fixes it (its varied inputs "
+                             f'are {varied})')
+        p = chain_priors[k]
+        if p.kind == sampling.NORMAL:
+            raise ValueError(f"'{k}': a surrogate's box is uniform or log-uniform, its prior is normal")
+        box = (10.0 ** p.a, 10.0 ** p.b) if p.kind == sampling.LOGUNIFORM else (p.a, p.b)
+        if not is_var:
+            if not inside(_box_coordinate(p, PEM_V0_NOMINAL[k]), p):
+                raise ValueError(f"'{k}' is pinned at {PEM_V0_NOMINAL[k]}, outside the surrogate's box [{box[0]}, {box[1]}]")
+            continue
+        for pres, row in zip(np.atleast_1d(pressures), sweeps):
+            q = row[k]
+            if q.kind == p.kind:
+                lo, hi = q.a, q.b
+            else:
+                ends = (10.0 ** q.a, 10.0 ** q.b) if q.kind == sampling.LOGUNIFORM else (q.a, q.b)
+                lo, hi = (_box_coordinate(p, v) for v in ends)
+            if not (inside(lo, p) and inside(hi, p)):
+                ends = (10.0 ** q.a, 10.0 ** q.b) if q.kind == sampling.LOGUNIFORM else (q.a, q.b)
+                raise ValueError(f"'{k}' is swept over [{ends[0]}, {ends[1]}] at {float(pres):g} Torr, outside the surrogate's box "
+                                 f'[{box[0]}, {box[1]}]')
+    rows, is_log, a, w = [], [], [], []
+    for k in varied:                                  # the chain's external slots: its varied inputs in COUPLED_INPUTS order
+        p = chain_priors[k]
+        rows.append(COUPLED_INPUTS.index(k))
+        if p.kind != sampling.NORMAL:
+            is_log.append(p.kind == sampling.LOGUNIFORM)
+            a.append(p.a)
+            w.append(np.float64(p.b) - np.float64(p.a))
+        else:                                         # (a plume-only input, not examined: never read by the launch's stages)
+            is_log.append(False)
+            a.append(0.0)
+            w.append(1.0)
+    return SweepSlotMap(rows, is_log, a, w)

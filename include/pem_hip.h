@@ -661,6 +661,46 @@ int pem_sobol_sweep_f64_dev(int group, size_t n_base, uint64_t first_index, uint
                             double spike_threshold, int max_attempts, const double* clip, double* j0_out, double* partial,
                             uint64_t* flags, int n_blocks, pem_stream_t stream);
 
+/* ---- the same study through the chained surrogate (csrc/pem_surrogate_sobol.hip) ----------------------------------------------
+ * scripts/pem_v0/sobol.py:70-98: model() takes V_cc, T and u_ion(z = L_ch) from `SURR.predict` of the component chain; only j_ion
+ * goes to the true plume model.  ONE launch covers the Cathode or the Thruster group at every pressure, with the chain's cathode
+ * table (and, for the Thruster group, the coupling map and the thruster table) in the analytic stages' place; the plume table is
+ * checked and never read.  PEM_SWEEP_PLUME is refused: that group stays on pem_sobol_sweep_f64_dev.
+ * group, n_base, first_index, seed, n_p, kind, a, b: as pem_sobol_sweep_f64_dev.
+ * Streams: row r (0: A, 1: B) of group g at pressure p is stream 2 (g n_p + p) + r, base samples first_index ..: exactly
+ *   pem_sobol_sweep_f64_dev's rows (attempt 0) for the same seed and tables, so a model sweep and a surrogate sweep see one design.
+ * n_dim, vcc_slot, ib0_slot, stages, vcc_lo, vcc_w: the chain, as pem_sparse_predict_chain_fields_f64_dev takes it (the thruster
+ *   table has 2 + u_rank outputs).  The I_B0 slot is never written.
+ * slot_row, slot_log, slot_a, slot_w: HOST arrays [n_dim - 2]; entry k describes the k-th external coordinate (row k of the
+ *   parents' t: the slots other than vcc_slot and ib0_slot, in order) and reads input row slot_row[k] (0 .. 14, distinct).
+ *   Coordinates:  u = slot_log[k] ? log10(x) : x;  t = 2.0 * (u - slot_a[k]) / slot_w[k] - 1.0, left to right, no contraction,
+ *   slot_w = b - a formed in fp64 by the caller (calibration.SurrogatePosterior.assemble_inputs' expression).  A varied input takes
+ *   x from the design row, any other input its pin a[p][row].  Every input the group varies must have a slot.
+ * u_rank (0 .. 14), u_dof, u_norm, u_scale, u_basis: the thruster stage's field as pem_sparse_predict_chain_fields_f64_dev takes
+ *   it (u_lat0 == 2); u_cell (0 .. u_dof - 1): the one cell of the profile the study reads.
+ * QoIs: Cathode V_cc; Thruster T (the thruster table's output 1) and u = denorm(v), v = 0; v = fma(l_q, u_basis[u_cell][q], v).
+ *   With u_rank == 0 the u column of every output is NaN.
+ * f_out (DEVICE [n_p][nv + 2][nq][n_base] or NULL): every f; evaluation 0 is row A, 1 row B, 2 + j row A with varied input j
+ *   from B.  For tests: production passes NULL.
+ * partial: DEVICE [n_p][n_blocks][2 + 4 nv][nq], rows and nq as pem_sobol_sweep_f64_dev's, one deterministic partial per workgroup.
+ * flags: DEVICE [n_p][n_blocks][2] counts over the evaluations: non-physical thruster values (T < 0 or I_B0 < 0), and V_cc
+ *   coupling coordinates outside [-1, 1] (the thruster table is extrapolated there; counted for the Cathode group too).
+ * Bit contracts (tests/test_chain_sobol.py):
+ *   1. Every f equals, bit for bit, the V_cc / T row and column u_cell of u_field that
+ *      pem_sparse_predict_chain_fields_f64_dev gives at the same coordinates (u_rank == 0: pem_sparse_predict_chain_f64_dev's rows).
+ *      An AB evaluation whose swapped input the cathode table does not read reuses row A's V_cc coordinate: the same bits.
+ *   2. An f depends on seed, the sample's index first_index + i, the tables and the chain only -- not on n_base, n_blocks or
+ *      whether f_out is asked for.
+ * LDS: the larger of the cathode's and (Thruster group) the thruster's outer bases, n_dim coordinates per thread and about 2 KB
+ * of accumulators and tables, at most 160 KB; above 64 KB it is requested as the chained launches request it.  Every argument is
+ * checked before the device is.                                                                                              */
+int pem_chain_sobol_sweep_f64_dev(int group, size_t n_base, uint64_t first_index, uint64_t seed, int n_p, const int32_t* kind,
+                                  const double* a, const double* b, int n_dim, int vcc_slot, int ib0_slot,
+                                  const pem_surr_stage* stages, double vcc_lo, double vcc_w, const int32_t* slot_row,
+                                  const int32_t* slot_log, const double* slot_a, const double* slot_w, int u_rank, int u_dof,
+                                  int u_norm, double u_scale, const double* u_basis, int u_cell, double* f_out, double* partial,
+                                  uint64_t* flags, int n_blocks, pem_stream_t stream);
+
 /* ---- differential evolution over the prior's quantile cube (csrc/pem_de.hip, hallthrusterpem_amd/optimize.py) ---------------
  * Stands in for run_mle(optimizer='evolution') (scripts/pem_v0/mcmc.py:170-231): scipy's differential_evolution semantics
  * (best1bin or rand1bin, F ~ U(mut_lo, mut_hi) once per generation, binomial crossover with probability cr and one forced
