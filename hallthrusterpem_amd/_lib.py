@@ -17,6 +17,7 @@ PEM_OK, PEM_ERR_INVALID_ARG, PEM_ERR_HIP, PEM_ERR_NO_DEVICE = 0, 1, 2, 3
 NANGLE = 91
 FUSED_LATENT_MAX_RANK = 8     # PEM_FUSED_LATENT_MAX_RANK (include/pem_hip.h): latents the fused model -> compression launch keeps
 FUSED_SYSTEM_MAX_RECORDS = 1024   # PEM_FUSED_SYSTEM_MAX_RECORDS: records (and conditions) of the fused multi-QoI likelihood's LDS table
+FUSED_SYSTEM_MAX_RADII = 8        # PEM_FUSED_SYSTEM_MAX_RADII: sweep radii of pem_coupled_system_loglik_radii_f64_dev
 SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of that table
 SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI groups of pem_sobol_sweep_f64_dev
 DE_MAX_POP, DE_MAX_DIM = 1024, 16   # PEM_DE_MAX_POP / PEM_DE_MAX_DIM: population and dimensions of pem_de_step_f64_dev
@@ -58,6 +59,10 @@ SIGNATURES = {
                                           + [_dp] * 5 + [_dp]),
     'pem_coupled_system_predict_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int]
                                            + [_dp] * 4 + [_sz, _dp, _dp]),
+    'pem_coupled_system_loglik_radii_f64_dev': (C.c_int, [_sz, _f8, C.c_int, _dp] + [_dp] * 15
+                                                + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int] + [_dp] * 5 + [_dp]),
+    'pem_coupled_system_predict_radii_f64_dev': (C.c_int, [_sz, _f8, C.c_int, _dp] + [_dp] * 15
+                                                 + [C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _f8, _f8, C.c_int] + [_dp] * 4 + [_sz, _dp, _dp]),
     'pem_predictive_inputs_f64_dev': (C.c_int, [_sz, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, _dp, _dp, _sz, C.c_int,
                                                 _dp, C.c_uint32, _dp, _sz, _dp]),
     'pem_predictive_noise_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _sz, _dp]),

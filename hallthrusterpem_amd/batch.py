@@ -173,24 +173,36 @@ class CoupledBatch:
         _lib.check(rc)
         return out
 
+    def _system_entry(self, lk, what):
+        """(entry point, its arguments between torr2pa and the inputs) of a `SystemLikelihood`: the one-radius launch at the batch's
+        radius, or -- for a table of j_ion records at several sweep radii -- the launch that takes the likelihood's list of radii
+        (a host array, copied into the kernel arguments by the call; the batch's own radius plays no part)"""
+        lib = _lib.load()
+        radii = getattr(lk, 'sweep_radii', (lk.sweep_radius,))   # (a hand-made one-radius table need not carry the tuple)
+        if len(radii) > 1:
+            arr = (C.c_double * len(radii))(*radii)
+            return getattr(lib, f'pem_coupled_system_{what}_radii_f64_dev'), (len(radii), arr)
+        if lk.sweep_radius != self.radius:
+            raise ValueError(f'the likelihood\'s j_ion data are at r = {lk.sweep_radius}, the batch sweeps r = {self.radius}')
+        return getattr(lib, f'pem_coupled_system_{what}_f64_dev'), (self.radius,)
+
     def run_system_loglik(self, likelihood, out=None, stream=None):
         """Coupled evaluation + the multi-QoI log-likelihood of a `likelihood.SystemLikelihood` in one launch
-        (`pem_coupled_system_loglik_f64_dev`): the j_ion records are reduced against the profile in LDS, the V_cc, T and u_ion
-        records in the per-sample epilogue.  Sample i belongs to condition i mod n_cond.  Returns the (n,) per-sample sums;
+        (`pem_coupled_system_loglik_f64_dev`; `pem_coupled_system_loglik_radii_f64_dev` when the likelihood holds j_ion at several
+        sweep radii): the j_ion records are reduced against the profile in LDS, the V_cc, T and u_ion records in the per-sample
+        epilogue.  Sample i belongs to condition i mod n_cond.  Returns the (n,) per-sample sums;
         V_cc / div_angle / T_c / invalid are written as by `run`."""
         import torch
         s = torch.cuda.current_stream(self.device) if stream is None else stream
         if self.layout != 'soa':
             raise NotImplementedError("the fused likelihood launch reads SoA inputs: use layout='soa'")
         lk = likelihood
-        if lk.sweep_radius != self.radius:
-            raise ValueError(f'the likelihood\'s j_ion data are at r = {lk.sweep_radius}, the batch sweeps r = {self.radius}')
         if out is None:
             out = torch.empty(self.n, dtype=torch.float64, device=self.device)
         p = lambda t: C.c_void_p(t.data_ptr())                                   # noqa: E731
         z0, z1, ncells = lk.uion_grid
-        rc = _lib.load().pem_coupled_system_loglik_f64_dev(
-            self.n, constants.TORR_2_PA, self.radius, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
+        fn, where = self._system_entry(lk, 'loglik')
+        rc = fn(self.n, constants.TORR_2_PA, *where, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
             p(lk.node), z0, z1, ncells, p(self.qoi[0]), p(self.qoi[1]), p(self.qoi[2]), p(out), p(self.invalid),
             C.c_void_p(s.cuda_stream))
         _lib.check(rc)
@@ -206,16 +218,14 @@ class CoupledBatch:
         if self.layout != 'soa':
             raise NotImplementedError("the fused prediction launch reads SoA inputs: use layout='soa'")
         lk = likelihood
-        if lk.sweep_radius != self.radius:
-            raise ValueError(f'the likelihood\'s j_ion data are at r = {lk.sweep_radius}, the batch sweeps r = {self.radius}')
+        fn, where = self._system_entry(lk, 'predict')
         rows = -(-self.n // lk.n_cond)
         if (pred.dtype != torch.float64 or pred.dim() != 2 or pred.device != self.device or pred.stride(1) != 1
                 or pred.shape[0] < rows or pred.shape[1] < lk.n_rec):
             raise ValueError(f'pred must be a float64 ({rows}, >= {lk.n_rec}) tensor on {self.device} with unit column stride')
         p = lambda t: C.c_void_p(t.data_ptr())                                   # noqa: E731
         z0, z1, ncells = lk.uion_grid
-        rc = _lib.load().pem_coupled_system_predict_f64_dev(
-            self.n, constants.TORR_2_PA, self.radius, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
+        rc = fn(self.n, constants.TORR_2_PA, *where, *self._in_ptrs, lk.n_cond, lk.n_rec, p(lk.rec), p(lk.span), lk.n_node,
             p(lk.node), z0, z1, ncells, *([p(self.qoi[0]), p(self.qoi[1]), p(self.qoi[2])] if qoi else [None] * 3), p(pred),
             pred.stride(0), p(self.invalid) if qoi else None, C.c_void_p(s.cuda_stream))
         _lib.check(rc)

@@ -318,6 +318,9 @@ class SurrogatePosterior(BatchedPosterior):
         `pem_chain_fields_loglik_f64_dev`: all four quantities of `QOI_MAP['System']`); otherwise uion is refused
         (`surrogate_input_map`)."""
         import torch
+        if len(likelihood.sweep_radii) > 1:
+            raise ValueError(f'the likelihood holds j_ion at several sweep radii {likelihood.sweep_radii}: the plume surrogate is '
+                             f'trained at one radius')
         if not likelihood.use_discharge:
             discharge = None
         self.surrogate = surrogate

@@ -333,6 +333,9 @@ class ChainedSurrogate:
         as well); the likelihood's `uion_grid` must be the chain's.  Without it they give NaN."""
         import torch
         lk = likelihood
+        if len(lk.sweep_radii) > 1:         # (the radius bits of its j_ion records must never reach pem_chain_*)
+            raise ValueError(f'the likelihood holds j_ion at several sweep radii {lk.sweep_radii}: the plume surrogate is trained at '
+                             f'one radius')
         st, _keep = self.stage_tables()
 
         def f64(x, what):

@@ -93,6 +93,15 @@ struct SystemPredict : SystemTable {
     long long ld_pred;
 };
 
+// several sweep radii (JMODE 8 / 9): JMODE 6 / 7's table with the fourth word of a j_ion record carrying k | (ridx << 8), ridx an
+// index into `radii` (pem_coupled_system_loglik_radii_f64_dev); `pred` is unused in JMODE 8.  The radii travel in the kernel
+// arguments: no device allocation, no copy to wait for.
+constexpr int SYS_RADII_MAX = PEM_FUSED_SYSTEM_MAX_RADII;
+struct SystemRadii : SystemPredict {
+    int n_radii;
+    double radii[SYS_RADII_MAX];
+};
+
 // the per-sample inputs of one lane, prefetched one tile ahead
 template <bool COUPLED>
 struct SampleIn {
@@ -187,6 +196,10 @@ __device__ __forceinline__ SampleIn<true> generate_sample(const McDesign& mc, co
 //               records of the sample's condition in the epilogue (system_epilogue_sum)
 //            7: record predictions -- JMODE 6's table, the model value of every record stored instead of compared
 //               (j_ion in the rounds, jion_records_store; the others in the epilogue, system_epilogue_store)
+//            8, 9: JMODE 6 and 7 against j_ion measured at 2 .. 8 sweep radii, still ONE model evaluation per sample.  The profile
+//               is j_ion(r, alpha_k) = base(r) g(alpha_k) + j_cex(r) and the shape g = A1 exp(-(alpha/a1)^2) + A2 exp(-(alpha/a2)^2)
+//               does not depend on r: the rounds stage g (the angle loop with amplitudes A1, A2 and no j_cex), the sample's pairs
+//               {base(r), j_cex(r)} sit beside it, and a record applies the pair of its radius to the interpolated g.
 // LDS map (doubles): shared by the workgroup: simpson[96][2] | dpoly[32*12];  per wave: params[NROWS][64] |
 // tile[S*91] | 2 (sink).  The Simpson table is padded with zero weights to L*CH <= 96 entries so the angle loop
 // needs no branch (NSIMP, TABLE_DOUBLES: csrc/pem_plume.h).  The den/num partial sums of a round reuse the rows of
@@ -200,7 +213,7 @@ constexpr int QPOLY_DOUBLES = (PEM_NDI + PEM_NQB) * PEM_NDC * 2;
 template <int L, int JMODE>
 constexpr int wave_lds_doubles() {
     return param_rows<L>() * WAVE +
-           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5 || JMODE == 6 || JMODE == 7) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
+           ((JMODE == 1 || JMODE == 3 || JMODE == 4 || JMODE == 5 || JMODE == 6 || JMODE == 7 || JMODE == 8 || JMODE == 9) ? (WAVE / L) * NANG + 2 : JMODE == 2 ? ((WAVE / L) * NANG + 4) / 2 : 0);
 }
 template <int L, int JMODE>
 constexpr int fast_lds_doubles() { return TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>(); }
@@ -218,6 +231,9 @@ struct WaveLds {
     int n_unode;
     double* pred;            // JMODE 7: the [draws][ld_pred] predictions in HBM
     long long ld_pred;
+    const double* rtab;      // JMODE 8 / 9: [n_radii][3] {r, 1 / r^2, 1 / (2 pi r^2)}
+    double2* pairs;          // JMODE 8 / 9: this wave's [S][n_radii] {base(r), j_cex(r)} of the round's samples
+    int n_radii;
     const double2* simpson;  // [96] {cden, cnum}
     const double* poly;      // [32*12]
     const double2* qpoly;    // reduced-QoI mode: [(32+64)*12] {Qd, Qn} coefficients of the Simpson functionals, or nullptr
@@ -451,8 +467,22 @@ __device__ __forceinline__ unsigned count_round(unsigned ctx_off, unsigned tile_
 
 // Fused likelihood modes (JMODE 3 / 6): lane c's share -- records c, c+L, ... -- of the n_rec j_ion records {weight, y, 1/std, k}
 // of one sample against its staged profile row; the L chunk lanes of the sample are summed by the caller.
-template <int L, typename JT>
-__device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec, const JT* row, int c) {
+// RADII (JMODE 8 / 9): `row` holds the shape g and the record's fourth word k | (ridx << 8); the model value is
+// base(r) g + j_cex(r) with the pair {base, j_cex} of radius ridx (clamped into the sample's n_radii pairs).
+template <bool RADII>
+__device__ __forceinline__ double jion_model(const double4& e, double lo_v, double hi_v, const double2* pairs, int n_radii) {
+    const double v = fma(e.x, hi_v - lo_v, lo_v);
+    if constexpr (RADII) {
+        const double2 p = pairs[min((int)((__double_as_longlong(e.w) >> 8) & 0xff), n_radii - 1)];
+        return fma(p.x, v, p.y);
+    } else {
+        return v;
+    }
+}
+
+template <int L, typename JT, bool RADII = false>
+__device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec, const JT* row, int c, const double2* pairs = nullptr,
+                                                   int n_radii = 0) {
     double acc = 0.0;
     constexpr int MU = PEM_LOGLIK_MU;   // records in flight per lane: the k -> row[k] chain is two LDS latencies deep
     for (int a0 = c; a0 < n_rec; a0 += MU * L) {
@@ -468,7 +498,7 @@ __device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec,
         }
 #pragma unroll
         for (int u = 0; u < MU; ++u) {
-            const double model = fma(e[u].x, hi_v[u] - lo_v[u], lo_v[u]);
+            const double model = jion_model<RADII>(e[u], lo_v[u], hi_v[u], pairs, n_radii);
             const double z = (e[u].y - model) * e[u].z;
             if (a0 + u * L < n_rec) acc = fma(-0.5 * z, z, acc);
         }
@@ -477,8 +507,9 @@ __device__ __forceinline__ double jion_records_sum(const double4* mt, int n_rec,
 }
 
 // JMODE 7: lane c's share of the j_ion records of one sample, the model values JMODE 6 compares, stored to out[record]
-template <int L, typename JT>
-__device__ __forceinline__ void jion_records_store(const double4* mt, int n_rec, const JT* row, int c, double* out) {
+template <int L, typename JT, bool RADII = false>
+__device__ __forceinline__ void jion_records_store(const double4* mt, int n_rec, const JT* row, int c, double* out,
+                                                   const double2* pairs = nullptr, int n_radii = 0) {
     constexpr int MU = PEM_LOGLIK_MU;
     for (int a0 = c; a0 < n_rec; a0 += MU * L) {
         double4 e[MU];
@@ -493,7 +524,7 @@ __device__ __forceinline__ void jion_records_store(const double4* mt, int n_rec,
         }
 #pragma unroll
         for (int u = 0; u < MU; ++u)
-            if (a0 + u * L < n_rec) out[a0 + u * L] = fma(e[u].x, hi_v[u] - lo_v[u], lo_v[u]);
+            if (a0 + u * L < n_rec) out[a0 + u * L] = jion_model<RADII>(e[u], lo_v[u], hi_v[u], pairs, n_radii);
     }
 }
 
@@ -557,6 +588,8 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     constexpr int CH = (NANG + L - 1) / L;  // angles per lane
     constexpr int TILE = S * NANG;          // profile values per round tile
     constexpr bool WRITE_J = JMODE != 0;
+    constexpr bool RADII = JMODE == 8 || JMODE == 9;   // several sweep radii: the tile holds the shape g, the radii come in as pairs
+    constexpr bool PREDICT = JMODE == 7 || JMODE == 9;
     using JT = typename std::conditional<JMODE == 2, float, double>::type;   // element type of the stored profile
     constexpr int PER16 = 16 / (int)sizeof(JT);                              // values per 16-byte piece
     constexpr int PAIRS = TILE / PER16;     // 16-byte pieces of a full round tile (TILE divides evenly)
@@ -590,10 +623,14 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     const double u1 = 1.0 / (a1 * a1), u2 = 1.0 / (a2 * a2);
     const double A1 = (1.0 - in.c0) / normaliser(a1, u1, m.poly);  // plume.py:64-73
     const double A2 = in.c0 / normaliser(a2, u2, m.poly);          // plume.py:75-85
-    // plume.py:95-100 at the single radius
-    const double decay = exp(-rad * n_neutral * in.sigma);
-    const double j_cex = I_B0 * (1.0 - decay) * inv_2pi_r2;
-    const double base = I_B0 * decay * inv_r2;
+    // plume.py:95-100 at the single radius (several radii: the rounds form the pairs {base(r), j_cex(r)}; the loop below runs on
+    // the amplitudes A1, A2 alone)
+    double j_cex = 0.0, base = 1.0;
+    if constexpr (!RADII) {
+        const double decay = exp(-rad * n_neutral * in.sigma);
+        j_cex = I_B0 * (1.0 - decay) * inv_2pi_r2;
+        base = I_B0 * decay * inv_r2;
+    }
     const unsigned long long a1_nonpos = __ballot(a1 <= 0.0);  // plume.py:105, first term
     unsigned long long inv_mask = 0;
     double den = 0.0, num = 0.0;
@@ -660,6 +697,16 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
             }
             const double q1 = r01 * r01, q2 = r02 * r02;
             double den = 0.0, num = 0.0, lo = __builtin_inf();   // this lane's chunk of the round (shadows the tile sums)
+            double2* pairs = nullptr;
+            if constexpr (RADII) {
+                // plume.py:95-98 at every radius, one exp per (sample, radius): lane (s, c) takes radii c, c + L of its sample
+                pairs = m.pairs + s * m.n_radii;
+                const double nn = __shfl(n_neutral, smp), sg = __shfl(in.sigma, smp), ib = __shfl(I_B0, smp);
+                for (int r = c; r < m.n_radii; r += L) {
+                    const double decay = exp(-m.rtab[3 * r] * nn * sg);
+                    pairs[r] = make_double2(ib * decay * m.rtab[3 * r + 1], ib * (1.0 - decay) * m.rtab[3 * r + 2]);
+                }
+            }
             // The weight reads are issued PF iterations ahead IN SOURCE ORDER: the tile stores in between are
             // LDS stores the compiler must assume may alias the table, so it cannot hoist the reads itself.
             constexpr int PF = 6;
@@ -710,36 +757,64 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
                     }
                 }
             }
+            if constexpr (RADII) {
+                // div_angle and T_c are those of the last radius: its Simpson sums are the shape's scaled by base(r_last) -- a
+                // vanished beam (base = 0) still gives the reference's 0 / 0
+                wave_lds_sync();
+                const double bl = pairs[m.n_radii - 1].x;
+                den *= bl;
+                num *= bl;
+            }
             // this round has read its nine parameter rows of sample `smp`: rows 2c, 2c+1 now carry the partial sums
             params[(2 * c) * WAVE + smp] = den;
             params[(2 * c + 1) * WAVE + smp] = num;
             // plume.py:105: invalid if alpha1 <= 0 or any j_ion <= 0 (NaN compares false).  Without a stored profile
             // the minimum runs over f and j_cex is added once: rounding is monotonic, min_k fl(f_k + c) = fl(min_k f_k + c).
-            unsigned long long bad = __ballot((WRITE_J ? lo : lo + jcex) <= 0.0);
+            unsigned long long bad;
+            if constexpr (RADII) {
+                // any j_ion(r, alpha_k) <= 0 at ANY radius: with base > 0 the smallest value of a radius is base min_k g + j_cex
+                // (rounding is monotonic); any other pair -- never under the priors -- is decided value by value
+                bool any = false;
+                for (int r = 0; r < m.n_radii; ++r) {
+                    const double2 p = pairs[r];
+                    if (p.x > 0.0 && __builtin_isfinite(p.x) && __builtin_isfinite(p.y)) {
+                        any = any || fma(p.x, lo, p.y) <= 0.0;
+                    } else {
+                        for (int j = 0; j < CH; ++j)
+                            if (k0 + j < NANG) any = any || fma(p.x, (double)tile[s * NANG + k0 + j], p.y) <= 0.0;
+                    }
+                }
+                bad = __ballot(any);
+            } else {
+                bad = __ballot((WRITE_J ? lo : lo + jcex) <= 0.0);
+            }
 #pragma unroll
             for (int sh = S; sh < WAVE; sh <<= 1) bad |= bad >> sh;   // fold the L chunk lanes of a sample onto bit s
             bad = (bad | (a1_nonpos >> (round * S))) & ((S == 64) ? ~0ull : ((1ull << S) - 1));
             inv_mask |= bad << (round * S);
             if constexpr (WRITE_J) {
                 if ((bad >> s) & 1) {  // plume.py:106: the whole profile of an invalid sample becomes 1e-20 (rare)
-                    const JT fill = (JT)1e-20;
+                    const JT fill = RADII ? (JT)0.0 : (JT)1e-20;   // (several radii: 0 g + 1e-20 at every radius)
                     for (int j = 0; j < CH; ++j)
                         if (k0 + j < NANG) tile[s * NANG + k0 + j] = fill;
+                    if constexpr (RADII) {   // (program order: every lane of the sample has read its pairs above)
+                        for (int r = c; r < m.n_radii; r += L) pairs[r] = make_double2(0.0, 1e-20);
+                    }
                 }
                 wave_lds_sync();
                 const long long first = t * WAVE + (long long)round * S;
-                if constexpr (JMODE == 3 || JMODE == 6 || JMODE == 7) {
+                if constexpr (JMODE == 3 || JMODE == 6 || JMODE == 7 || RADII) {
                     static_assert(2 * L < param_rows<L>(), "row 2L of `params` carries the likelihood sum");
                     // measured current densities against the staged profile: lane (s, c) takes measurements c, c+L, ...
                     // of its sample's condition (sample index mod n_cond); the sample's sum goes to row 2L of `params`
                     const unsigned cond = ((unsigned)((t * WAVE) % io.n_cond) + (unsigned)(round * S + s)) % (unsigned)io.n_cond;
                     const JT* row = tile + s * NANG;
-                    if constexpr (JMODE == 7) {   // the values themselves, to the sample's row of pred
+                    if constexpr (PREDICT) {   // the values themselves, to the sample's row of pred
                         const int2 sp = m.span[4 * cond + PEM_SYS_JION];
                         if (FULL || first + s < io.n) {
                             const unsigned u = (unsigned)((t * WAVE) % io.n_cond) + (unsigned)(round * S + s);
-                            jion_records_store<L>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c,
-                                                  pred_row(m, t, u, io.n_cond) + sp.x);
+                            jion_records_store<L, JT, RADII>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c,
+                                                             pred_row(m, t, u, io.n_cond) + sp.x, pairs, m.n_radii);
                         }
                         wave_lds_sync();
                         continue;
@@ -750,7 +825,7 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
                         acc = jion_records_sum<L>(mt, io.n_ang, row, c);
                     } else {
                         const int2 sp = m.span[4 * cond + PEM_SYS_JION];
-                        acc = jion_records_sum<L>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c);
+                        acc = jion_records_sum<L, JT, RADII>(reinterpret_cast<const double4*>(m.meas) + sp.x, sp.y, row, c, pairs, m.n_radii);
                     }
 #pragma unroll
                     for (int sh = S; sh < WAVE; sh <<= 1) acc += __shfl_xor(acc, sh);   // the L chunk lanes of sample s
@@ -823,13 +898,13 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     if constexpr (JMODE == 3) {
         if (live) io.loglik[g] = params[(2 * L) * WAVE + lane];
     }
-    if constexpr (JMODE == 6) {
+    if constexpr (JMODE == 6 || JMODE == 8) {
         if (live) {
             const unsigned cond = ((unsigned)((t * WAVE) % io.n_cond) + (unsigned)lane) % (unsigned)io.n_cond;
             io.loglik[g] = system_epilogue_sum(params[(2 * L) * WAVE + lane], m, cond, V_cc, thrust, v_exh);
         }
     }
-    if constexpr (JMODE == 7) {
+    if constexpr (PREDICT) {
         if (live) {
             const unsigned u = (unsigned)((t * WAVE) % io.n_cond) + (unsigned)lane;
             system_epilogue_store(m, u % (unsigned)io.n_cond, V_cc, thrust, v_exh, pred_row(m, t, u, io.n_cond));
@@ -837,11 +912,11 @@ __device__ __forceinline__ void process_tile(const PlumeIO& io, const CoupledIO&
     }
     if (live) {
         // (the record predictions take V_cc, div_angle and T_c as optional outputs)
-        if (JMODE != 7 || io.div) io.div[g] = acos(cos_div);
-        if (have_T && (JMODE != 7 || io.Tc)) io.Tc[g] = thrust * cos_div;
+        if (!PREDICT || io.div) io.div[g] = acos(cos_div);
+        if (have_T && (!PREDICT || io.Tc)) io.Tc[g] = thrust * cos_div;
         if (io.invalid) io.invalid[g] = (uint8_t)((inv_mask >> lane) & 1);
         if constexpr (COUPLED) {
-            if (JMODE != 7 || cio.V_cc) cio.V_cc[g] = V_cc;
+            if (!PREDICT || cio.V_cc) cio.V_cc[g] = V_cc;
             if (cio.I_B0) cio.I_B0[g] = I_B0;
             if (cio.T) cio.T[g] = thrust;
         }
@@ -862,7 +937,9 @@ struct NoDesign {};
 template <bool MC, int JMODE = 0>
 using DesignArg = typename std::conditional<
     MC, McDesign,
-    typename std::conditional<JMODE == 6, SystemTable, typename std::conditional<JMODE == 7, SystemPredict, NoDesign>::type>::type>::type;
+    typename std::conditional<JMODE == 6, SystemTable,
+                              typename std::conditional<JMODE == 7, SystemPredict,
+                                                        typename std::conditional<JMODE >= 8, SystemRadii, NoDesign>::type>::type>::type>::type;
 
 // bytes of LDS the counting modes add per workgroup: brackets' {loh, words} [91][NQ] | below counters [NQ][91] | premask thresholds [91] x 16
 template <int NQ, bool PM>
@@ -921,7 +998,10 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, 
     m.n_unode = 0;
     m.pred = nullptr;
     m.ld_pred = 0;
-    if constexpr (JMODE == 6 || JMODE == 7) {   // records | spans | u_ion denominators behind the per-wave regions (system_lds_bytes)
+    m.rtab = nullptr;
+    m.pairs = nullptr;
+    m.n_radii = 0;
+    if constexpr (JMODE == 6 || JMODE == 7 || JMODE == 8 || JMODE == 9) {   // records | spans | u_ion denominators behind the per-wave regions (system_lds_bytes)
         double* meas = lds + TABLE_DOUBLES + WPB * wave_lds_doubles<L, JMODE>();
         for (int i = tid; i < 4 * mc.n_rec; i += WAVE * WPB) meas[i] = mc.rec[i];
         int2* span = reinterpret_cast<int2*>(meas + 4 * mc.n_rec);
@@ -937,9 +1017,22 @@ void plume_r1_kernel(PlumeIO io, CoupledIO cio, long long ntiles, DesignArg<MC, 
         m.span = span;
         m.unode = unode;
         m.n_unode = mc.n_node;
-        if constexpr (JMODE == 7) {
+        if constexpr (JMODE == 7 || JMODE == 9) {
             m.pred = mc.pred;
             m.ld_pred = mc.ld_pred;
+        }
+        if constexpr (JMODE == 8 || JMODE == 9) {   // behind them: the radii's constants | every wave's pairs of a round (radii_lds_bytes)
+            const int nr = min(max(mc.n_radii, 1), SYS_RADII_MAX);
+            double* rtab = unode + (((mc.n_node > 2 ? mc.n_node : 2) + 1) & ~1);
+            if (tid < nr) {
+                const double r = mc.radii[tid];
+                rtab[3 * tid] = r;
+                rtab[3 * tid + 1] = 1.0 / (r * r);
+                rtab[3 * tid + 2] = 1.0 / (2.0 * PEM_PI * (r * r));
+            }
+            m.rtab = rtab;
+            m.pairs = reinterpret_cast<double2*>(rtab + ((3 * nr + 1) & ~1)) + wave * (WAVE / L) * nr;
+            m.n_radii = nr;
         }
     }
 
@@ -1100,6 +1193,12 @@ size_t system_lds_bytes(int n_cond, const SystemTable& tab) {
     return (size_t)tab.n_rec * 32 + (size_t)n_cond * 32 + (size_t)(tab.n_node > 2 ? tab.n_node : 2) * 8;
 }
 
+// JMODE 8 / 9 behind that table (padded to 16 bytes): {r, 1 / r^2, 1 / (2 pi r^2)} [n_radii] | pairs [WPB][samples of a round][n_radii] double2
+size_t radii_lds_bytes(int n_cond, const SystemRadii& tab, int samples_per_round) {
+    return ((system_lds_bytes(n_cond, tab) + 15) & ~(size_t)15) + (size_t)((3 * tab.n_radii + 1) & ~1) * 8 +
+           (size_t)WPB * samples_per_round * tab.n_radii * 16;
+}
+
 template <int L, int JMODE, bool MC, int NQ = 0, bool PM = false>
 size_t r1_lds_bytes(const PlumeIO& io) {
     size_t lds = (size_t)fast_lds_doubles<L, JMODE>() * 8;
@@ -1141,10 +1240,11 @@ int r1_per_cu(size_t lds, long long* per_cu) {
 // `grid_only`: report the grid the launch would use (the counting modes size their record buffer by it) and launch nothing
 template <int L, bool COUPLED, int JMODE, bool MC = false, int NQ = 0, bool PM = false>
 int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McDesign& mc = McDesign{}, unsigned* grid_only = nullptr,
-              const SystemTable* sys = nullptr, const SystemPredict* pr = nullptr) {
+              const SystemTable* sys = nullptr, const SystemPredict* pr = nullptr, const SystemRadii* rd = nullptr) {
     size_t lds = r1_lds_bytes<L, JMODE, MC, NQ, PM>(io);
     if constexpr (JMODE == 6) lds += system_lds_bytes(io.n_cond, *sys);
     if constexpr (JMODE == 7) lds += system_lds_bytes(io.n_cond, *pr);
+    if constexpr (JMODE == 8 || JMODE == 9) lds += radii_lds_bytes(io.n_cond, *rd, WAVE / L);
     const long long ntiles = (io.n + WAVE - 1) / WAVE;
     unsigned grid = 0;
     auto kern = plume_r1_kernel<L, COUPLED, JMODE, MC, NQ, PM>;
@@ -1163,6 +1263,7 @@ int launch_r1(const PlumeIO& io, const CoupledIO& cio, hipStream_t st, const McD
     if constexpr (MC) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, mc);
     else if constexpr (JMODE == 6) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *sys);
     else if constexpr (JMODE == 7) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *pr);
+    else if constexpr (JMODE == 8 || JMODE == 9) hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, *rd);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVE * WPB), lds, st, io, cio, ntiles, NoDesign{});
     HIP_TRY(hipGetLastError());
     return PEM_OK;
@@ -1486,6 +1587,77 @@ int pem_coupled_system_predict_f64_dev(size_t n, double torr2pa, double radius, 
     pr.pred = pred;
     pr.ld_pred = (long long)ld_pred;
     return launch_r1<4, true, 7>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, nullptr, &pr);
+}
+
+// ---- the same two launches against j_ion measured at several sweep radii: one model evaluation per sample (JMODE 8 / 9) ------
+// every check of the two entry points that needs no device; `who` names the entry point in the message
+static int check_system_radii(const char* who, int n_radii, const double* radii, int n_cond, int n_rec, int n_node, int ncells) {
+    if (n_radii < 2 || n_radii > PEM_FUSED_SYSTEM_MAX_RADII)
+        return fail(PEM_ERR_INVALID_ARG, "%s: 2 <= n_radii <= %d (PEM_FUSED_SYSTEM_MAX_RADII), got %d", who, PEM_FUSED_SYSTEM_MAX_RADII, n_radii);
+    if (!radii) return fail(PEM_ERR_INVALID_ARG, "%s: NULL radii", who);
+    for (int r = 0; r < n_radii; ++r) {
+        if (!(std::isfinite(radii[r]) && radii[r] > 0.0)) return fail(PEM_ERR_INVALID_ARG, "%s: radii must be finite and positive, radii[%d] = %g", who, r, radii[r]);
+        if (r > 0 && !(radii[r] > radii[r - 1])) return fail(PEM_ERR_INVALID_ARG, "%s: radii must be strictly ascending, radii[%d] = %g after %g", who, r, radii[r], radii[r - 1]);
+    }
+    if (n_cond < 1 || n_cond > PEM_FUSED_SYSTEM_MAX_RECORDS || n_rec < 0 || n_rec > PEM_FUSED_SYSTEM_MAX_RECORDS || n_node < 0 ||
+        n_node > 2 * PEM_FUSED_SYSTEM_MAX_RECORDS)
+        return fail(PEM_ERR_INVALID_ARG, "%s: 1 <= n_cond <= %d, 0 <= n_rec <= %d, 0 <= n_node <= %d (PEM_FUSED_SYSTEM_MAX_RECORDS)", who,
+                    PEM_FUSED_SYSTEM_MAX_RECORDS, PEM_FUSED_SYSTEM_MAX_RECORDS, 2 * PEM_FUSED_SYSTEM_MAX_RECORDS);
+    if (n_node > 0 && ncells < 2) return fail(PEM_ERR_INVALID_ARG, "%s: need at least 2 u_ion grid points", who);
+    return PEM_OK;
+}
+
+static SystemRadii system_radii_arg(int n_radii, const double* radii, int n_rec, const double* rec, const int32_t* span, int n_node,
+                                    const int32_t* node, double z0, double z1, int ncells, double* pred, size_t ld_pred) {
+    SystemRadii rd;
+    static_cast<SystemTable&>(rd) = SystemTable{rec, span, node, n_rec, n_node, z0, z1, ncells};
+    rd.pred = pred;
+    rd.ld_pred = (long long)ld_pred;
+    rd.n_radii = n_radii;
+    for (int r = 0; r < SYS_RADII_MAX; ++r) rd.radii[r] = radii[r < n_radii ? r : n_radii - 1];
+    return rd;
+}
+
+int pem_coupled_system_loglik_radii_f64_dev(size_t n, double torr2pa, int n_radii, const double* radii, const double* P_b,
+                                            const double* V_a, const double* T_e, const double* V_vac, const double* Pstar,
+                                            const double* P_T, const double* mdot_a, const double* a_1, const double* c0,
+                                            const double* c1, const double* c2, const double* c3, const double* c4, const double* c5,
+                                            const double* sigma_cex, int n_cond, int n_rec, const double* rec, const int32_t* span,
+                                            int n_node, const int32_t* node, double z0, double z1, int ncells, double* V_cc,
+                                            double* div_angle, double* T_c, double* loglik, uint8_t* invalid, pem_stream_t stream) {
+    if (int rc = check_system_radii("pem_coupled_system_loglik_radii", n_radii, radii, n_cond, n_rec, n_node, ncells)) return rc;
+    if (n == 0) return PEM_OK;
+    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !mdot_a || !a_1 || !c0 || !c1 || !c2 || !c3 || !c4 || !c5 ||
+        !sigma_cex || (n_rec > 0 && !rec) || !span || (n_node > 0 && !node) || !V_cc || !div_angle || !T_c || !loglik)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_loglik_radii: NULL array");
+    if (int rc = check_device()) return rc;
+    PlumeIO io{(long long)n, torr2pa, radii[n_radii - 1], P_b, c0, c1, c2, c3, c4, c5, sigma_cex, nullptr, nullptr, nullptr, div_angle, T_c, invalid, nullptr,
+               nullptr, nullptr, nullptr, nullptr, loglik, n_cond, 0};
+    CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
+    const SystemRadii rd = system_radii_arg(n_radii, radii, n_rec, rec, span, n_node, node, z0, z1, ncells, nullptr, 0);
+    return launch_r1<4, true, 8>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, nullptr, nullptr, &rd);
+}
+
+int pem_coupled_system_predict_radii_f64_dev(size_t n, double torr2pa, int n_radii, const double* radii, const double* P_b,
+                                             const double* V_a, const double* T_e, const double* V_vac, const double* Pstar,
+                                             const double* P_T, const double* mdot_a, const double* a_1, const double* c0,
+                                             const double* c1, const double* c2, const double* c3, const double* c4, const double* c5,
+                                             const double* sigma_cex, int n_cond, int n_rec, const double* rec, const int32_t* span,
+                                             int n_node, const int32_t* node, double z0, double z1, int ncells, double* V_cc,
+                                             double* div_angle, double* T_c, double* pred, size_t ld_pred, uint8_t* invalid,
+                                             pem_stream_t stream) {
+    if (int rc = check_system_radii("pem_coupled_system_predict_radii", n_radii, radii, n_cond, n_rec, n_node, ncells)) return rc;
+    if (ld_pred < (size_t)n_rec) return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict_radii: ld_pred < n_rec");
+    if (n == 0) return PEM_OK;
+    if (!P_b || !V_a || !T_e || !V_vac || !Pstar || !P_T || !mdot_a || !a_1 || !c0 || !c1 || !c2 || !c3 || !c4 || !c5 ||
+        !sigma_cex || (n_rec > 0 && !rec) || !span || (n_node > 0 && !node) || !pred)
+        return fail(PEM_ERR_INVALID_ARG, "pem_coupled_system_predict_radii: NULL array");
+    if (int rc = check_device()) return rc;
+    PlumeIO io{(long long)n, torr2pa, radii[n_radii - 1], P_b, c0, c1, c2, c3, c4, c5, sigma_cex, nullptr, nullptr, nullptr, div_angle, T_c, invalid, nullptr,
+               nullptr, nullptr, nullptr, nullptr, nullptr, n_cond, 0};
+    CoupledIO cio{V_a, T_e, V_vac, Pstar, P_T, mdot_a, a_1, V_cc, nullptr, nullptr};
+    const SystemRadii rd = system_radii_arg(n_radii, radii, n_rec, rec, span, n_node, node, z0, z1, ncells, pred, ld_pred);
+    return launch_r1<4, true, 9>(io, cio, static_cast<hipStream_t>(stream), McDesign{}, nullptr, nullptr, nullptr, &rd);
 }
 
 // ---- coupled, mixed precision: fp64 arithmetic, the 91-point profile stored as fp32 -----------------

@@ -8,7 +8,8 @@ profiles (csrc/pem_likelihood.hip); the sum over conditions and the log-sum-exp 
 The reference scripts are stale and untested: parity unpinned.
 
 `SystemLikelihood` is the measurement table of the other quantities of the reference's `System` calibration as well -- cathode
-coupling voltage, thrust, ion velocity -- for the fused launch `pem_coupled_system_loglik_f64_dev` (mcmc.py:28-45,57-104).
+coupling voltage, thrust, ion velocity -- for the fused launch `pem_coupled_system_loglik_f64_dev` (mcmc.py:28-45,57-104); with
+`sweep_radii` the current densities may be measured at several sweep radii (`pem_coupled_system_loglik_radii_f64_dev`).
 """
 import ctypes as C
 
@@ -78,7 +79,14 @@ class SystemLikelihood:
                  the reference's DATA, std = sqrt(var_y) (mcmc.py:80).  `y` / `var_y` are (Ne,) for 'V_cc' and 'T';
                  (Ne, Nz) for 'uion' with `loc` the (Nz,) axial positions [m] inside the u_ion grid; (Ne, Na) for 'jion'
                  with `loc` the (Na, 2) rows (r, alpha) of the sweep, every r equal to `sweep_radius` and |alpha| <= pi/2.
-    :param sweep_radius: the plume's sweep radius [m] (the j_ion model is evaluated there).
+    :param sweep_radius: the plume's sweep radius [m] (the j_ion model is evaluated there); default 1.0.  Given together with
+                 `sweep_radii` it must equal their last radius.
+    :param sweep_radii: None, or 2 .. 8 strictly ascending positive sweep radii [m] for a probe sweep taken at several distances
+                 (the reference's data schema gives ion current density the coordinates (r, theta): hallmd/data.py).  Every r of the
+                 j_ion `loc` must then equal one of them exactly; a j_ion record carries k | (ridx << 8), and the table is evaluated
+                 by `pem_coupled_system_loglik_radii_f64_dev` / `_predict_radii_` -- one model evaluation per sample whatever the
+                 number of radii.  `sweep_radius` is then the last (largest) radius, the one div_angle and T_c refer to
+                 (`data.pem_to_xarray`'s convention).  One radius is the scalar path.  `sweep_radii` (a tuple) is always set.
     :param uion_grid: (z0, z1, num_cells) of the u_ion profile: z_c = z0 + (z1 - z0) c / (num_cells - 1).  The default
                  (0.0, 0.08, 200) is the grid `models.thruster` uses at the default fidelity (2, 2): num_cells = 50 (f0 + 2)
                  on domain [0, 0.08] (thruster.py:99-107).
@@ -90,8 +98,23 @@ class SystemLikelihood:
     condition, each condition's block padded to an odd number of records (its LDS reads spread over the banks).
     """
 
-    def __init__(self, data, sweep_radius: float = 1.0, uion_grid=UION_GRID, qois=None, device=None):
+    def __init__(self, data, sweep_radius: float | None = None, sweep_radii=None, uion_grid=UION_GRID, qois=None, device=None):
         import torch
+        if sweep_radii is not None:
+            radii = np.asarray(sweep_radii, dtype=np.float64).reshape(-1)
+            limit = _lib.FUSED_SYSTEM_MAX_RADII
+            if not 1 <= radii.size <= limit:
+                raise ValueError(f'sweep_radii takes 1 .. PEM_FUSED_SYSTEM_MAX_RADII = {limit} radii, got {radii.size}')
+            if not np.all(np.isfinite(radii) & (radii > 0.0)):
+                raise ValueError(f'sweep_radii must be finite and positive, got {tuple(radii)}')
+            if not np.all(np.diff(radii) > 0.0):
+                raise ValueError(f'sweep_radii must be strictly ascending, got {tuple(radii)}')
+            if sweep_radius is not None and float(sweep_radius) != radii[-1]:
+                raise ValueError(f'sweep_radius = {sweep_radius} conflicts with sweep_radii = {tuple(radii)}: with several radii the '
+                                 f'scalar is their last one (leave it out)')
+            sweep_radius = radii[-1]
+        elif sweep_radius is None:
+            sweep_radius = 1.0
         if qois is None:
             unknown = [q for q in data if q not in QOIS]
             if unknown:
@@ -113,6 +136,7 @@ class SystemLikelihood:
         self.component = next((k for k, v in QOI_MAP.items() if v == qois), None)
         self.use_discharge = self.component != 'Cathode'            # mcmc.py:100-101
         self.sweep_radius = float(sweep_radius)
+        self.sweep_radii = (self.sweep_radius,) if sweep_radii is None else tuple(float(r) for r in radii)
         z0, z1, ncells = float(uion_grid[0]), float(uion_grid[1]), int(uion_grid[2])
         if not (ncells >= 2 and z1 > z0):
             raise ValueError(f'uion_grid = (z0, z1, num_cells) needs z1 > z0 and num_cells >= 2, got {tuple(uion_grid)}')
@@ -141,6 +165,8 @@ class SystemLikelihood:
                 pos = np.minimum(np.abs(loc[:, 1]) / GRID_STEP, 90.0)       # JionLikelihood's (k, w), bit for bit
                 k = np.minimum(np.floor(pos).astype(np.int32), 89)
                 w, bits = pos - k, k.astype(np.int64)
+                if len(self.sweep_radii) > 1:                               # the index of the record's radius above the angle index
+                    bits = bits | (np.searchsorted(self.sweep_radii, loc[:, 0]).astype(np.int64) << 8)
             else:   # uion: between the nodes of the kernels' own grid doubles
                 z = self._uion_nodes(z0, z1, ncells)
                 k = np.clip(np.searchsorted(z, loc, side='right') - 1, 0, ncells - 2)
@@ -182,7 +208,11 @@ class SystemLikelihood:
             loc = np.asarray(d.get('loc'), dtype=np.float64)
             if loc.ndim != 2 or loc.shape[1] != 2 or loc.shape[0] < 1:
                 raise ValueError(f"jion: 'loc' must be (Na, 2) rows of (r, alpha), got shape {loc.shape}")
-            if not np.all(loc[:, 0] == self.sweep_radius):
+            if len(self.sweep_radii) > 1:
+                if not np.all(np.isin(loc[:, 0], self.sweep_radii)):
+                    raise ValueError(f'jion: every radius of loc must equal one of sweep_radii = {self.sweep_radii} exactly, got '
+                                     f'{np.unique(loc[:, 0])}')
+            elif not np.all(loc[:, 0] == self.sweep_radius):
                 raise ValueError(f'jion: every radius of loc must equal sweep_radius = {self.sweep_radius} (one sweep radius '
                                  f'per dataset), got {np.unique(loc[:, 0])}')
             if not np.all(np.abs(loc[:, 1]) <= np.pi / 2 + 1e-12):

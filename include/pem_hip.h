@@ -285,6 +285,37 @@ int pem_coupled_system_predict_f64_dev(size_t n, double torr2pa, double radius, 
                                        double* div_angle, double* T_c, double* pred, size_t ld_pred, uint8_t* invalid,
                                        pem_stream_t stream);
 
+/* The two launches above against ion current density measured at SEVERAL sweep radii (the reference's data schema gives it the
+ * coordinates (r, theta): hallmd/data.py), still one model evaluation per sample.  plume.py:95-102 for one sample is
+ *   j_ion(r, alpha_k) = base(r) g(alpha_k) + j_cex(r),   g = A1 exp(-(alpha/alpha1)^2) + A2 exp(-(alpha/alpha2)^2),
+ *   decay(r) = exp(-r n sigma), base(r) = I_B0 decay(r) / r^2, j_cex(r) = I_B0 (1 - decay(r)) / (2 pi r^2):
+ * the 91-point shape g does not depend on r, so it is staged once and a sample keeps n_radii pairs {base, j_cex}.
+ * radii: HOST array of n_radii sweep radii [m], 2 <= n_radii <= PEM_FUSED_SYSTEM_MAX_RADII, finite, > 0, strictly ascending;
+ * copied into the kernel arguments by the call.  Table, span and node as above, except that a PEM_SYS_JION record's fourth word is
+ * k | (ridx << 8) (int64 bit pattern; k < 90, ridx an index into radii, clamped into it by the kernel):
+ *   model = fma(base(r_ridx), fma(w, g[k+1] - g[k], g[k]), j_cex(r_ridx)).
+ * A sample is non-physical (plume.py:104-107 over all radii) when alpha1 <= 0 or any j_ion(r, alpha_k) <= 0 at ANY of the radii;
+ * every j_ion record of such a sample, at every radius, sees 1e-20, and `invalid` is that all-radii flag.  div_angle and T_c are
+ * those of the last (largest) radius.  Everything else -- the other kinds, optional outputs, limits -- as the one-radius launches.
+ * A malformed call returns PEM_ERR_INVALID_ARG before any device call.                                                          */
+#define PEM_FUSED_SYSTEM_MAX_RADII 8
+int pem_coupled_system_loglik_radii_f64_dev(size_t n, double torr2pa, int n_radii, const double* radii, const double* P_b,
+                                            const double* V_a, const double* T_e, const double* V_vac, const double* Pstar,
+                                            const double* P_T, const double* mdot_a, const double* a_1, const double* c0,
+                                            const double* c1, const double* c2, const double* c3, const double* c4,
+                                            const double* c5, const double* sigma_cex, int n_cond, int n_rec, const double* rec,
+                                            const int32_t* span, int n_node, const int32_t* node, double z0, double z1,
+                                            int ncells, double* V_cc, double* div_angle, double* T_c, double* loglik,
+                                            uint8_t* invalid, pem_stream_t stream);
+int pem_coupled_system_predict_radii_f64_dev(size_t n, double torr2pa, int n_radii, const double* radii, const double* P_b,
+                                             const double* V_a, const double* T_e, const double* V_vac, const double* Pstar,
+                                             const double* P_T, const double* mdot_a, const double* a_1, const double* c0,
+                                             const double* c1, const double* c2, const double* c3, const double* c4,
+                                             const double* c5, const double* sigma_cex, int n_cond, int n_rec, const double* rec,
+                                             const int32_t* span, int n_node, const int32_t* node, double z0, double z1,
+                                             int ncells, double* V_cc, double* div_angle, double* T_c, double* pred,
+                                             size_t ld_pred, uint8_t* invalid, pem_stream_t stream);
+
 /* pem_coupled_f64_dev + pem_svd_compress_f64_dev in one launch: latent[i][r] = sum_k norm(j_ion[i][k]) basis[k][r]
  * accumulated in the registers of the angle loop, one lane per sample (csrc/pem_latent.hip) -- the profile is neither
  * stored nor staged (120 + 24 + 8 rank bytes per evaluation).  norm: PEM_NORM_NONE or PEM_NORM_LOG10; basis: [91][rank] device array, rank <=
