@@ -22,6 +22,7 @@ SYS_JION, SYS_VCC, SYS_T, SYS_UION = 0, 1, 2, 3   # PEM_SYS_*: record kinds of t
 SWEEP_CATHODE, SWEEP_THRUSTER, SWEEP_PLUME = 0, 1, 2   # PEM_SWEEP_*: the QoI groups of pem_sobol_sweep_f64_dev
 DE_MAX_POP, DE_MAX_DIM = 1024, 16   # PEM_DE_MAX_POP / PEM_DE_MAX_DIM: population and dimensions of pem_de_step_f64_dev
 DE_BEST1BIN, DE_RAND1BIN = 0, 1     # PEM_DE_*: its strategies
+DRAM_MAX_DIM = 32                   # PEM_DRAM_MAX_DIM: dimensions of pem_dram_step_f64_dev (one lane per dimension)
 CHAIN_TIME_BLOCK = 4096             # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
 MARGINALS_MAX_PAR, MARGINALS_MAX_BINS = 32, 64   # PEM_MARGINALS_MAX_PAR / _MAX_BINS: parameters and bins of pem_chain_hist_f64_dev
 HIST_ROW_TILE = 128                 # PEM_HIST_ROW_TILE: rows it bins per stage
@@ -120,6 +121,8 @@ SIGNATURES = {
                                                 C.c_int, _dp]),
     'pem_de_step_f64_dev': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, _f8, _dp, _dp, _dp, _dp, _dp, _dp,
                                       _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
+    'pem_dram_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_uint64, _f8, _f8, C.c_uint64, C.c_uint64, C.c_uint64, _sz, C.c_uint64]
+                                        + [_dp] * 13 + [_dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

@@ -26,6 +26,9 @@ quantity from its own dataset at its own operating conditions (`likelihood.Syste
 `SurrogatePosterior` is that flow as the reference runs it: the trained component surrogates (`chain.ChainedSurrogate`) in the
 model's place, j_ion rebuilt from its SVD latents and I_D taken from the surrogate's output, all in ONE launch
 (`pem_chain_system_loglik_f64_dev`) -- what a plugged-in thruster solver that costs seconds per sample needs.
+
+`DRAM` restates the reference's sampler as torch operations around two posterior evaluations per step; `DeviceDRAM` is the same
+algorithm with the sampler's own work in one launch per step (`pem_dram_step_f64_dev`) and both proposals in ONE evaluation.
 """
 import ctypes as C
 import math
@@ -561,3 +564,134 @@ class DRAM:
     def acceptance(self):
         """(2, K): fraction of steps accepted at the first and at the delayed stage"""
         return self.accepted.double() / max(1, self.steps)
+
+
+class DeviceDRAM:
+    """`DRAM` with the whole sampler on the device: K chains of delayed-rejection adaptive Metropolis, one launch of
+    `pem_dram_step_f64_dev` (csrc/pem_dram.hip) per step.  That launch resolves the step whose two proposals were just
+    evaluated -- accept decisions, point, Welford moments, adaptation of L, trace row -- and draws both proposals of the next
+    step, so a step is [log_posterior(prop) ; the launch], with `use_graph` one hipGraph replay, and nothing runs on the host
+    between steps.  The keywords are `DRAM`'s and mean what they mean there; the draws are Philox4x32-10 keyed by `seed`
+    (include/pem_hip.h), not torch's generator, so the two samplers visit different states.
+
+    log_posterior: callable on a (2K, d) float64 device tensor returning (2K,) values, as `DifferentialEvolution`'s f takes
+    (P, d).  Rows k and K + k are chain k's first-stage and delayed-stage proposals.  ITS VALUE MUST NOT DEPEND ON THE ROW:
+    a closed form, or `.log_posterior` of a `SystemPosterior` / `JionPosterior` / `SurrogatePosterior` built with
+    n_chains=2K, shared_nuisance=True, fresh_nuisance=False.  Otherwise a chain's kept logp and its next proposal would be
+    judged under different nuisance draws.
+
+    The constructor evaluates theta0 once, through the same 2K-row call, and draws the proposals of step 1.  `run` continues
+    across calls: run(a) followed by run(b) visits the states of run(a + b).  There is no CPU path."""
+
+    def __init__(self, log_posterior, theta0, cov0=None, n_chains: int | None = None, seed: int = 0, adapt_after: int = 5000,
+                 adapt_interval: int = 1000, eps: float = 1e-12, gamma: float = 0.1, device=None, use_graph: bool = True):
+        import torch
+        if isinstance(theta0, torch.Tensor):
+            if device is None:
+                device = theta0.device
+            theta0 = theta0.detach().cpu().numpy()
+        t0 = np.atleast_1d(np.asarray(theta0, dtype=np.float64))
+        if t0.ndim == 1:
+            t0 = np.broadcast_to(t0, (int(n_chains or 1), t0.size))
+        if t0.ndim != 2 or t0.shape[0] < 1:
+            raise ValueError('theta0 must be (d,) or (K, d)')
+        self.K, self.d = t0.shape
+        if not 1 <= self.d <= _lib.DRAM_MAX_DIM:
+            raise ValueError(f'DeviceDRAM samples 1 to {_lib.DRAM_MAX_DIM} parameters (got {self.d})')
+        if device is not None and torch.device(device).type != 'cuda':
+            raise ValueError(f"DeviceDRAM runs on the GPU only (got device '{device}'): use DRAM for CPU tensors")
+        if not gamma > 0.0 or eps < 0.0 or int(adapt_interval) < 1 or int(adapt_after) < 0:
+            raise ValueError('need gamma > 0, eps >= 0, adapt_interval >= 1 and adapt_after >= 0')
+        c0 = np.eye(self.d) if cov0 is None else np.asarray(cov0, dtype=np.float64)
+        if c0.ndim == 1:
+            c0 = np.diag(c0)
+        if c0.shape != (self.d, self.d):
+            raise ValueError(f'cov0 must be ({self.d},) or ({self.d}, {self.d})')
+        self.f, self.seed, self.use_graph = log_posterior, int(seed), bool(use_graph)
+        self.adapt_after, self.adapt_interval, self.eps, self.gamma = int(adapt_after), int(adapt_interval), float(eps), float(gamma)
+        dev = self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        K, d = self.K, self.d
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=dev)                # noqa: E731
+        self.theta = torch.as_tensor(np.ascontiguousarray(t0), device=dev).clone()
+        self.L = torch.linalg.cholesky(torch.as_tensor(c0, device=dev)).expand(K, d, d).contiguous()
+        self.mean, self.scatter = self.theta.clone(), z(K, d, d)                             # running moments of the chain
+        self.prop, self.prop_logp = z(2, K, d), z(2, K)
+        self.state, self.accepted, self.flags = z(K, dt=torch.int64), z(2, K, dt=torch.int64), z(K, dt=torch.int32)
+        self.steps = 0
+        self._trace = self._logp_trace = None
+        self._window = (0, 0, 1)                                                             # trace_first, trace_len, thin
+        self._graph, self._graph_key = None, None
+        self.prop.copy_(self.theta.expand(2, K, d))
+        self.logp = self.f(self.prop.view(2 * K, d))[:K].clone()
+        self._launch()                                                                       # launch 0: the proposals of step 1
+
+    def _launch(self):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                    # noqa: E731
+        first, length, thin = self._window
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_dram_step_f64_dev(
+                self.K, self.d, self.seed, self.gamma, self.eps, self.adapt_after, self.adapt_interval, first, length, thin,
+                p(self.theta), p(self.logp), p(self.L), p(self.mean), p(self.scatter), p(self.prop), p(self.prop_logp),
+                p(self.state), p(self.accepted), p(self.flags), p(self._trace), p(self._logp_trace), None,
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _step(self):
+        self.prop_logp.view(-1).copy_(self.f(self.prop.view(2 * self.K, self.d)))
+        self._launch()
+
+    def _prepare(self):
+        """the graph is (re)recorded when a trace buffer or the trace window moves: a recorded launch carries them by value.
+        The steps that recording runs are undone."""
+        key = (self._trace.data_ptr() if self._trace is not None else 0,
+               self._logp_trace.data_ptr() if self._logp_trace is not None else 0) + self._window
+        if not self.use_graph or (self._graph is not None and self._graph_key == key):
+            return
+        kept = (self.theta, self.logp, self.L, self.mean, self.scatter, self.prop, self.prop_logp, self.state, self.accepted,
+                self.flags)
+        saved = [t.clone() for t in kept]
+        self._graph = None                                                                   # (frees the old recording first)
+        self._graph, _ = capture_graph(self._step, self.device)
+        self._graph_key = key
+        for t, s in zip(kept, saved):
+            t.copy_(s)
+
+    def run(self, n_steps: int, keep: bool = True, thin: int = 1, keep_logp: bool = False):
+        """Advance every chain n_steps.  Returns the (ceil(n_steps / thin), K, d) trace as a device tensor if `keep` -- steps
+        1, 1 + thin, ... of this call -- and with `keep_logp` the pair (trace, logp trace (ceil(n_steps / thin), K))."""
+        import torch
+        n_steps, thin = int(n_steps), int(thin)
+        if n_steps < 0 or thin < 1:
+            raise ValueError('n_steps >= 0 and thin >= 1')
+        rows = -(-n_steps // thin)
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)              # noqa: E731
+        self._trace = new(rows, self.K, self.d) if keep and rows else None
+        self._logp_trace = new(rows, self.K) if keep and keep_logp and rows else None
+        self._window = (self.steps, rows, thin) if self._trace is not None else (0, 0, 1)
+        if n_steps:
+            self._prepare()
+        for _ in range(n_steps):
+            if self.use_graph:
+                self._graph.replay()
+            else:
+                self._step()
+        self.steps += n_steps
+        trace, logp_trace = self._trace, self._logp_trace
+        if keep and trace is None:
+            trace = new(0, self.K, self.d)
+            logp_trace = new(0, self.K) if keep_logp else None
+        self._trace = self._logp_trace = None
+        self._window = (0, 0, 1)
+        if not keep:
+            return None
+        return (trace, logp_trace) if keep_logp else trace
+
+    @property
+    def acceptance(self):
+        """(2, K): fraction of steps accepted at the first and at the delayed stage"""
+        return self.accepted.double() / max(1, self.steps)
+
+    @property
+    def adaptation_failures(self) -> int:
+        """chains that skipped an adaptation because their covariance had a pivot that was not > 0 (`DRAM` would raise there)"""
+        return int((self.flags & 1).sum())

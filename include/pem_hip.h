@@ -756,6 +756,43 @@ int pem_de_step_f64_dev(int pop, int ndim, int strategy, int finalize, uint64_t 
                         double* pop_f, double* trial_u, const double* trial_f, double* theta, uint64_t* state, double* record,
                         double* history, size_t history_len, pem_stream_t stream);
 
+/* ---- delayed-rejection adaptive Metropolis, one launch per step (csrc/pem_dram.hip, calibration.DeviceDRAM) -----------------
+ * Stands in for uq.dram(fun, p0, niter, adapt_after, adapt_interval, eps, gamma) of run_mcmc (scripts/pem_v0/mcmc.py:275-300;
+ * uqtils is third-party and absent: parity UNPINNED, the algorithm is calibration.DRAM's) for n_chains chains of dimension
+ * ndim, one wave64 workgroup per chain.  All state is in DEVICE arrays of the caller:
+ *   theta [K][d], logp [K]        the current point and its log posterior
+ *   L [K][d][d]                   lower Cholesky factor of the proposal covariance, row-major
+ *   mean [K][d], scatter [K][d][d]  running moments of the chain (Welford); the start point is observation 1
+ *   prop [2][K][d]                the pending proposals y1 (block 0) and y2 (block 1): the caller evaluates the log posterior on
+ *   prop_logp [2][K]              prop seen as (2K, d) and writes the 2K values here between two launches
+ *   state [K]                     launches seen by the chain (the caller zeroes it; a captured graph advances it on every replay)
+ *   accepted [2][K]               acceptances per stage;   flags [K]: bit 0 = an adaptation was skipped (see 3.)
+ *   trace [trace_len][K][d], logp_trace [trace_len][K]   either may be NULL
+ *   draws NULL or [K][2d + 2]     z1[d], z2[d], u1, u2 as the launch used them for the step it resolved
+ * Launch s = state[k].  s == 0: nothing is pending.  s >= 1 resolves step s:
+ *   a1 = exp(min(lp1 - lp0, 0)) (a NaN difference stays NaN and is rejected), accepted when u1 < a1; otherwise y2 is accepted
+ *   when log(u2) < (lp2 - lp0) + log_q + log1p(-a1_rev) - log1p(-a1), a1_rev = exp(min(lp1 - lp2, 0)),
+ *   log_q = -(|w|^2 - |z1|^2) / 2, w = z1 - sqrt(gamma) z2 (= L^-1 (y1 - y2)); z1, z2 are recomputed from their counters.  Then
+ *   1. theta, logp and accepted are updated; with r = s - 1 - trace_first the point goes to row r / thin of the traces when
+ *      r >= 0, r mod thin == 0 and r / thin < trace_len;
+ *   2. count = s + 1, delta = theta - mean, mean += delta / count, scatter_ij += delta_i (theta_j - mean_j);
+ *   3. when s >= adapt_after and (s - adapt_after) mod adapt_interval == 0: L = the Cholesky factor (row by row, lower triangle
+ *      of the argument) of (2.4^2 / d) (scatter / (count - 1) + eps I), built in LDS and committed only if every pivot is > 0;
+ *      otherwise L is kept whole and bit 0 of flags[k] is set.
+ * Every launch then draws the proposals of step s + 1, y1_j = x_j + sum_{i<=j} L_ji z1_i and y2_j = x_j + sqrt(gamma) sum_{i<=j}
+ * L_ji z2_i (i ascending, products and sums rounded separately), and sets state[k] = s + 1.  The draws of step s are
+ * Philox4x32-10(counter = (chain, s mod 2^32, purpose, pair), key = seed): purposes 0x44520000 (z1), 0x44520001 (z2) -- pair p
+ * gives dimensions 2p and 2p + 1, each normcdfinv((2k + 1) 2^-53) of a 52-bit k -- and 0x44520002, whose pair 0 gives
+ * u1 = u53(x, y) and u2 = u53(z, w).  No atomics, no communication between workgroups: the same bits on every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: n_chains 0, ndim outside [1, PEM_DRAM_MAX_DIM], gamma not > 0,
+ * eps < 0, adapt_interval 0, thin 0, a NULL required array, a trace with trace_len 0.                                        */
+#define PEM_DRAM_MAX_DIM 32
+int pem_dram_step_f64_dev(size_t n_chains, int ndim, uint64_t seed, double gamma, double eps, uint64_t adapt_after,
+                          uint64_t adapt_interval, uint64_t trace_first, size_t trace_len, uint64_t thin, double* theta,
+                          double* logp, double* L, double* mean, double* scatter, double* prop, const double* prop_logp,
+                          uint64_t* state, uint64_t* accepted, uint32_t* flags, double* trace, double* logp_trace, double* draws,
+                          pem_stream_t stream);
+
 /* ---- MCMC chain diagnostics (hallthrusterpem_amd/diagnostics.py; the lag sums of uq.autocorrelation at
  * scripts/pem_v0/mcmc.py:310 -- uqtils, third-party, parity UNPINNED).  x: fp64 [n_rows][ld], unit column stride (a
  * (n, K, d) trace seen as n rows of K*d series; the pointer needs only 8-byte alignment).  Segment s is rows
