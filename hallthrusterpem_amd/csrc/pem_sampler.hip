@@ -91,6 +91,11 @@ int launch(size_t n, uint64_t first, uint64_t seed, uint32_t stream, int ndim, c
     if (!kind || !a || !b || !out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample: NULL array");
     if (!tiled && ld < n) return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample: leading dimension smaller than n");
     if (swap_dim < -2 || swap_dim >= ndim) return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample: swap_dim out of range");
+    for (int d = 0; d < ndim; ++d)
+        if (kind[d] < 0 || kind[d] > PEM_DIST_NORMAL)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample: unknown distribution kind %d for dimension %d", kind[d], d);
+    if (mode == 1 && (n_total == 0 || first > n_total || n > n_total - first))
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample_lhs: indices exceed n_total");
     if (n == 0) return PEM_OK;
     if (int rc = pem::check_device()) return rc;
     DimTable tab;
@@ -98,14 +103,10 @@ int launch(size_t n, uint64_t first, uint64_t seed, uint32_t stream, int ndim, c
         tab.kind[d] = d < ndim ? kind[d] : 0;
         tab.a[d] = d < ndim ? a[d] : 0.0;
         tab.b[d] = d < ndim ? b[d] : 0.0;
-        if (d < ndim && (kind[d] < 0 || kind[d] > PEM_DIST_NORMAL))
-            return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample: unknown distribution kind %d for dimension %d", kind[d], d);
     }
     int half_bits = 1;
-    if (mode == 1) {
-        if (n_total == 0 || first + n > n_total) return pem::fail(PEM_ERR_INVALID_ARG, "pem_sample_lhs: indices exceed n_total");
+    if (mode == 1)
         while ((1ull << (2 * half_bits)) < n_total) ++half_bits;
-    }
     size_t blocks = (n + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(sample_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (long long)n, first, seed, stream, ndim, tab,
