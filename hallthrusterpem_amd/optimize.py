@@ -5,6 +5,9 @@ Restates the steps of scripts/pem_v0/mcmc.py that come before `run_mcmc`:
     run_mle(optimizer='evolution')   mcmc.py:170-231   `DifferentialEvolution`: scipy's differential_evolution (best1bin /
                                                        rand1bin, dithered F, CR 0.7, deferred updating) with the whole
                                                        population evaluated as the rows of ONE posterior launch
+    run_mle(optimizer='nelder-mead') mcmc.py:170-231   `NelderMead`: scipy's bounded, adaptive Nelder-Mead (the default) for S
+                                                       simplices at once; the d + 4 points an iteration can ask for are the
+                                                       rows of ONE posterior launch, csrc/pem_nm.hip takes the decisions
     run_laplace / show_laplace       mcmc.py:234-265   `hessian` (central differences, 2 d^2 + 1 points in one call) and
                                                        `Laplace` (cov = pinv(-H), nearest positive-definite fall-back, draws)
     pdf_slice                        mcmc.py:132-148   `slices`: log prior, likelihood and posterior along every axis
@@ -159,6 +162,206 @@ class DifferentialEvolution:
         return DEResult(theta=self.theta[best].cpu().numpy(), u=self.pop_u[best].cpu().numpy(), value=float(rec[0]),
                         generations=c, converged=converged or bool(rec[2] == 1.0),
                         history=self.history[:c + 1].cpu().numpy())
+
+
+# -------------------------------------------------------------------------------------------------------- Nelder-Mead
+def search_bounds(names, priors=None):
+    """(lb, ub) of the search coordinates: the unit interval for a uniform or log-uniform prior, Phi(-+3) for a normal one
+    (the quantiles of `support`)"""
+    kind, _, _ = _table(names, priors)
+    lo, hi = 0.5 * math.erfc(3.0 / math.sqrt(2.0)), 0.5 * math.erfc(-3.0 / math.sqrt(2.0))
+    return (np.ascontiguousarray(np.where(kind == NORMAL, lo, 0.0)), np.ascontiguousarray(np.where(kind == NORMAL, hi, 1.0)))
+
+
+def quantile(theta, names, priors=None):
+    """The host inverse of the prior transform, theta (..., d) -> u: (theta - a) / (b - a) uniform, (log10 theta - a) / (b - a)
+    log-uniform, Phi((theta - a) / b) normal."""
+    kind, a, b = _table(tuple(names), priors)
+    t = np.asarray(theta, dtype=np.float64)
+    if t.ndim < 1 or t.shape[-1] != kind.size:
+        raise ValueError(f'theta must have one entry per name ({kind.size}) along its last axis')
+    u = np.empty_like(t)
+    erfc = np.vectorize(math.erfc, otypes=[np.float64])
+    for j, k in enumerate(kind):
+        if k == UNIFORM:
+            u[..., j] = (t[..., j] - a[j]) / (b[j] - a[j])
+        elif k == LOGUNIFORM:
+            u[..., j] = (np.log10(t[..., j]) - a[j]) / (b[j] - a[j])
+        else:
+            u[..., j] = 0.5 * erfc(-((t[..., j] - a[j]) / b[j]) / math.sqrt(2.0))
+    return u
+
+
+def nm_coefficients(d: int, adaptive: bool = True):
+    """(rho, chi, psi, sigma) as scipy's `_minimize_neldermead` writes them"""
+    if adaptive:
+        dim = float(d)
+        return 1.0, 1 + 2 / dim, 0.75 - 1 / (2 * dim), 1 - 1 / dim
+    return 1.0, 2.0, 0.5, 0.5
+
+
+def nm_simplex(x0, lb, ub, sim=None):
+    """scipy's initial simplex in search coordinates, (..., d + 1, d): x0 clipped into [lb, ub]; vertex k + 1 is x0 with
+    component k multiplied by 1.05, or set to 0.00025 where it is zero.  Then, for a caller's `sim` as well, entries above ub
+    are reflected into the interior (2 ub - x) and everything is clipped."""
+    if sim is None:
+        x0 = np.clip(np.asarray(x0, dtype=np.float64), lb, ub)
+        d = x0.shape[-1]
+        sim = np.repeat(x0[..., None, :], d + 1, axis=-2)
+        for k in range(d):
+            y = x0[..., k]
+            sim[..., k + 1, k] = np.where(y != 0, (1 + 0.05) * y, 0.00025)
+    sim = np.asarray(sim, dtype=np.float64)
+    sim = np.where(sim > ub, 2 * ub - sim, sim)
+    return np.ascontiguousarray(np.clip(sim, lb, ub))
+
+
+@dataclass
+class NMResult:
+    theta: np.ndarray        # (S, d) the best vertex of every simplex
+    u: np.ndarray            # (S, d) in search coordinates
+    value: np.ndarray        # (S,) f there
+    nit: np.ndarray          # (S,) scipy's nit: 1 + the iterations taken
+    nfev: np.ndarray         # (S,) the function values the sequential form would have spent
+    converged: np.ndarray    # (S,) bool: the simplex met xatol and fatol
+    operations: np.ndarray   # (S, 5) reflections, expansions, outside contractions, inside contractions, shrinks
+    best: int                # the simplex of the largest value (ties to the lowest index)
+    history: np.ndarray      # (launches, S) the best value of every simplex after each launch
+    final_simplex: tuple     # (sim (S, d + 1, d), fsim (S, d + 1)) in search coordinates, best vertex first
+
+
+class NelderMead:
+    """scipy's `minimize(method='Nelder-Mead', bounds=..., options={'adaptive': True, 'xatol': ..., 'fatol': ...})`
+    (run_mle's default optimizer, mcmc.py:170-231), MAXIMISING f, for S independent simplices on the device.
+
+    Every point an iteration can ask for -- the reflection, the expansion, both contractions and the d shrunk vertices -- is a
+    row of ONE call of f; `pem_nm_step_f64_dev` (csrc/pem_nm.hip, a workgroup per simplex) then takes scipy's decisions from
+    the values and emits the next d + 4 points.  The search runs in the prior's quantile cube, bounded by `search_bounds`.
+
+    f: callable (S (d + 4), d) float64 device tensor -> as many values (`.rows` of them), like `DifferentialEvolution`'s:
+       `post.log_posterior` of a posterior built with n_chains = nm.rows, shared_nuisance=True and fresh_nuisance=False (f is
+       compared across rows and across launches, so it must be a function of theta alone).
+    Exactly one of (all in theta): x0 (d,) or (S, d), from which scipy's initial simplex is built in search coordinates;
+    initial_simplex (d + 1, d) or (S, d + 1, d), e.g. the best d + 1 members of a DE population; n_starts Latin-hypercube points
+    of the quantile cube (the `Design` call that makes DE's initial population, keyed by `seed`).  With none, n_starts = 8:
+    a bounded simplex can be clipped flat onto a face of the box and stall there, which is what `NMResult.best` is for.
+    use_graph: an iteration (the launch and f's launches) is one hipGraph replay on one stream."""
+
+    def __init__(self, f, names, priors=None, x0=None, n_starts=None, initial_simplex=None, adaptive: bool = True,
+                 xatol: float = 1e-4, fatol: float = 1e-4, seed: int = 0, use_graph: bool = False, device=None):
+        self.names = tuple(names)
+        self.d = d = len(self.names)
+        if len(set(self.names)) != d or d < 1:
+            raise ValueError('names must be distinct and non-empty')
+        if d > _lib.NM_MAX_DIM:
+            raise ValueError(f'at most {_lib.NM_MAX_DIM} searched inputs (got {d})')
+        if sum(v is not None for v in (x0, n_starts, initial_simplex)) > 1:
+            raise ValueError('give at most one of x0, n_starts and initial_simplex')
+        if not (xatol >= 0.0 and fatol >= 0.0):
+            raise ValueError('xatol and fatol must be >= 0')
+        self.kind, self.a, self.b = _table(self.names, priors)
+        self.lb, self.ub = search_bounds(self.names, priors)
+        self._starts = None
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if x0.shape != (d,) and (x0.ndim != 2 or x0.shape[1] != d or x0.shape[0] < 1):
+                raise ValueError(f'x0 must have the shape ({d},) or (S, {d})')
+            with np.errstate(invalid='ignore', divide='ignore'):
+                q = quantile(x0.reshape(-1, d), self.names, priors)
+            if not np.isfinite(q).all():
+                raise ValueError('x0 has no finite quantile under the priors (a NaN, or a value <= 0 under a log-uniform prior)')
+            sim0 = nm_simplex(q, self.lb, self.ub)
+        elif initial_simplex is not None:
+            sim = np.asarray(initial_simplex, dtype=np.float64)
+            if sim.shape != (d + 1, d) and (sim.ndim != 3 or sim.shape[1:] != (d + 1, d) or sim.shape[0] < 1):
+                raise ValueError(f'initial_simplex must have the shape ({d + 1}, {d}) or (S, {d + 1}, {d})')
+            with np.errstate(invalid='ignore', divide='ignore'):
+                q = quantile(sim.reshape(-1, d + 1, d), self.names, priors)
+            if not np.isfinite(q).all():
+                raise ValueError('initial_simplex has no finite quantile under the priors (a NaN, or a value <= 0 under a '
+                                 'log-uniform prior)')
+            sim0 = nm_simplex(None, self.lb, self.ub, q)
+        else:
+            self._starts = 8 if n_starts is None else int(n_starts)
+            if self._starts < 1:
+                raise ValueError('n_starts must be >= 1')
+            sim0 = None
+        self.S = self._starts if sim0 is None else sim0.shape[0]
+        self.rows = self.S * (d + 4)
+        self.f, self.coef, self.adaptive = f, nm_coefficients(d, adaptive), bool(adaptive)
+        self.xatol, self.fatol, self.seed, self.use_graph = float(xatol), float(fatol), int(seed), bool(use_graph)
+
+        import torch
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if sim0 is None:
+            unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
+            u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(self.S, device=self.device, method='lhs').T
+            sim0 = nm_simplex(u0.cpu().numpy(), self.lb, self.ub)
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        self.sim0 = torch.as_tensor(sim0, device=self.device)
+        self.sim, self.fsim = z(self.S, d + 1, d), z(self.S, d + 1)
+        self.cand_x, self.cand_f, self.theta = z(self.S, d + 4, d), z(self.rows), z(self.rows, d)
+        self.state = z(self.S, _lib.NM_STATE_WORDS, dt=torch.int64)
+        self.history = z(0, self.S)
+        self._graph = None
+
+    def _launch(self, finalize: bool):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
+        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_nm_step_f64_dev(
+                self.S, self.d, 1 if finalize else 0, *self.coef, self.xatol, self.fatol, ptr(self.kind), ptr(self.a),
+                ptr(self.b), ptr(self.lb), ptr(self.ub), p(self.sim), p(self.fsim), p(self.cand_x), p(self.cand_f), p(self.theta),
+                p(self.state), p(self.history) if self.history.numel() else None, self.history.shape[0],
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _iteration(self):
+        self._launch(False)
+        self.cand_f.copy_(self.f(self.theta))
+
+    def reset(self):
+        """Back to the initial simplices (the next launch emits their vertices)."""
+        self.state.zero_()
+        self.sim.copy_(self.sim0)
+
+    def _prepare(self, n_launches: int):
+        """history room for n_launches; the graph is (re)recorded when the history buffer moves"""
+        import torch
+        if self.history.shape[0] < n_launches:
+            self.history = torch.full((n_launches, self.S), math.nan, dtype=torch.float64, device=self.device)
+            self._graph = None
+        if self.use_graph and self._graph is None:
+            self.reset()
+            self._graph, _ = capture_graph(self._iteration, self.device)
+        self.reset()
+
+    def run(self, max_iterations=None, check_every: int = 10) -> NMResult:
+        """Iterate until every simplex has converged (the host reads `state` every `check_every` launches) or scipy's `nit`
+        reaches `max_iterations` (default 200 d, scipy's maxiter): a simplex that does not converge ends with
+        nit == max_iterations.  scipy's maxfev, which can abort in the middle of an iteration, is not reproduced: `nfev` is
+        reported.  `converged` is the test on the simplex the search ends with."""
+        import torch
+        m = 200 * self.d if max_iterations is None else int(max_iterations)
+        if m < 1 or check_every < 1:
+            raise ValueError('max_iterations >= 1 and check_every >= 1')
+        self._prepare(m)
+        c = 0
+        for c in range(m):
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._iteration()
+            if c >= 1 and c % check_every == 0 and bool((self.state[:, 3] == 1).all().item()):
+                break
+        self._launch(True)                     # the last values are resolved; theta = every simplex's best vertex
+        torch.cuda.synchronize(self.device)
+        st = self.state.cpu().numpy()
+        sim, fsim = self.sim.cpu().numpy(), self.fsim.cpu().numpy()
+        value = fsim[:, 0].copy()
+        return NMResult(theta=self.theta.view(self.S, self.d + 4, self.d)[:, 0].cpu().numpy(), u=sim[:, 0].copy(), value=value,
+                        nit=st[:, 1].copy(), nfev=st[:, 2].copy(), converged=st[:, 3] == 1, operations=st[:, 4:9].copy(),
+                        best=int(np.argmax(value)), history=self.history[:c + 1].cpu().numpy(), final_simplex=(sim, fsim))
 
 
 # ----------------------------------------------------------------------------------------------------------- Laplace

@@ -756,6 +756,52 @@ int pem_de_step_f64_dev(int pop, int ndim, int strategy, int finalize, uint64_t 
                         double* pop_f, double* trial_u, const double* trial_f, double* theta, uint64_t* state, double* record,
                         double* history, size_t history_len, pem_stream_t stream);
 
+/* ---- bounded Nelder-Mead, many simplices, one launch per iteration (csrc/pem_nm.hip, optimize.NelderMead) -------------------
+ * Stands in for minimize(obj_fun, x0, method='Nelder-Mead', bounds=bds, tol=1e-4, options={'adaptive': True}) of run_mle
+ * (scripts/pem_v0/mcmc.py:170-231, the default optimizer): scipy's _minimize_neldermead for n_simplex independent simplices of
+ * dimension ndim, one wave64 workgroup each, MAXIMISING f over x in [lb, ub]^ndim (g = -f is minimised; a NaN f is g = +inf).
+ * Every point an iteration can ask for is emitted before it starts; the caller evaluates f on all of them between launches.
+ * kind/a/b (the prior table, theta = the prior transform of x, as pem_de_step_f64_dev) and lb/ub are HOST arrays of ndim.
+ * rho, chi, psi, sigma are scipy's coefficients (1, 2, 0.5, 0.5, or adaptive 1, 1 + 2/d, 0.75 - 1/(2d), 1 - 1/d).
+ * DEVICE arrays, S = n_simplex, d = ndim:
+ *   sim [S][d+1][d], fsim [S][d+1]   the simplex, best vertex first, and f there (a NaN f is stored as -inf)
+ *   cand_x [S][d+4][d]               the pending points; theta [S*(d+4)][d] their transform, the rows f is called on
+ *   cand_f [S][d+4]                  f of those rows, written by the caller between launches
+ *   state [S][PEM_NM_STATE_WORDS]    0 launches, 1 nit, 2 nfev, 3 status (0 running, 1 converged), 4-8 the counts of
+ *                                    reflections, expansions, outside contractions, inside contractions and shrinks, 9 the code
+ *                                    of the last operation (1 ... 5 in that order, 0 none).  The caller zeroes word 0.
+ *   history [history_len][S] or NULL   the best f after launch l >= 1 goes to row l - 1 when l - 1 < history_len
+ * By the launch counter l = state word 0 of a simplex:
+ *   l == 0  the caller's simplex (already inside the bounds) is emitted: rows 0 ... d are its vertices, rows d+1 ... d+3 repeat
+ *           vertex 0.  Words 1-9 are zeroed, l = 1.  With finalize nothing happens.
+ *   l == 1  rows 0 ... d of cand_f are the vertices' values: nit = 1, nfev = d + 1; sort, test, emit.
+ *   l >= 2  resolve: with gr, ge, gc, gcc the values of rows 0-3 and g the sorted simplex values,
+ *             gr < g[0]: the expansion (row 1) if ge < gr, else the reflection (row 0); nfev += 2
+ *             else gr < g[d-1]: the reflection; nfev += 1
+ *             else gr < g[d]: the outside contraction (row 2) if gc <= gr, else shrink; nfev += 2
+ *             else: the inside contraction (row 3) if gcc < g[d], else shrink; nfev += 2
+ *           the taken row replaces the worst vertex; a shrink replaces vertices 1 ... d by rows 4 ... d+3, nfev += d.  nit += 1.
+ *   sort    stable: the rank of vertex i is #{j : g_j < g_i or (g_j == g_i and j < i)}.
+ *   test    converged when max|sim[1:] - sim[0]| <= xatol and max|g[0] - g[1:]| <= fatol (a NaN or infinite difference is not).
+ *           A converged simplex is frozen: only its launch counter and its history column move from then on.
+ *   emit    (not converged, not finalize) with xbar = (((sim[0] + sim[1]) + ...) + sim[d-1]) / d and w = sim[d], each clipped as
+ *           min(max(., lb), ub), products and sums rounded separately:
+ *             row 0  (1 + rho) xbar - rho w           row 2  (1 + psi rho) xbar - psi rho w
+ *             row 1  (1 + rho chi) xbar - rho chi w   row 3  (1 - psi) xbar + psi w
+ *             rows 4 ... d+3  sim[0] + sigma (sim[j] - sim[0]), j = 1 ... d
+ *           and l += 1.
+ *   finalize  resolve, sort and test as above without emitting; all d + 4 rows of the simplex's block of theta become the
+ *           transform of its best vertex; l is kept.  The search cannot be continued after it.
+ * No atomics, no communication between workgroups: the same bits on every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: n_simplex 0, ndim outside [1, PEM_NM_MAX_DIM], a NULL array
+ * other than history, lb > ub, a negative or NaN tolerance, a history with history_len 0.                                  */
+#define PEM_NM_MAX_DIM 32
+#define PEM_NM_STATE_WORDS 10
+int pem_nm_step_f64_dev(size_t n_simplex, int ndim, int finalize, double rho, double chi, double psi, double sigma, double xatol,
+                        double fatol, const int32_t* kind, const double* a, const double* b, const double* lb, const double* ub,
+                        double* sim, double* fsim, double* cand_x, const double* cand_f, double* theta, uint64_t* state,
+                        double* history, size_t history_len, pem_stream_t stream);
+
 /* ---- delayed-rejection adaptive Metropolis, one launch per step (csrc/pem_dram.hip, calibration.DeviceDRAM) -----------------
  * Stands in for uq.dram(fun, p0, niter, adapt_after, adapt_interval, eps, gamma) of run_mcmc (scripts/pem_v0/mcmc.py:275-300;
  * uqtils is third-party and absent: parity UNPINNED, the algorithm is calibration.DRAM's) for n_chains chains of dimension
