@@ -10,7 +10,11 @@
      mean and covariance; the arrays are saved to posterior_marginals.npz;
   5. the three figures, only if matplotlib imports (it is not a dependency).
 
-    python examples/posterior_marginals.py [n_steps] [out.npz]          (default 600 DRAM steps of 16 chains)
+    python examples/posterior_marginals.py [--hex] [n_steps] [out.npz]          (default 600 DRAM steps of 16 chains)
+
+--hex: the pair panels as journal_plots draws them, hexagonal bins (corner(plot2d='hex'), matplotlib's hexbin rule at gridsize =
+bins); for the first pair of every group the number of hexagons at or above cmin and its 50 % / 90 % levels are printed, and the
+tables are saved with the rest.
 """
 import sys
 import time
@@ -25,8 +29,10 @@ from hallthrusterpem_amd.calibration import DRAM, SystemPosterior               
 from hallthrusterpem_amd.likelihood import SystemLikelihood                            # noqa: E402
 from hallthrusterpem_amd.predictive import Predictive                                  # noqa: E402
 
-n_steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
-out = Path(sys.argv[2]) if len(sys.argv) > 2 else Path('posterior_marginals.npz')
+hexagons = '--hex' in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != '--hex']
+n_steps = int(argv[0]) if len(argv) > 0 else 600
+out = Path(argv[1]) if len(argv) > 1 else Path('posterior_marginals.npz')
 rng = np.random.default_rng(0)
 op = lambda k: np.stack([10.0 ** rng.uniform(-6, -4.5, k), rng.uniform(250, 350, k), rng.uniform(4e-6, 6e-6, k)], 1)  # noqa: E731
 na = 25
@@ -71,7 +77,9 @@ for g, sel in groups.items():
         continue
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    c = marginals.corner(trace, names=names, select=sel, burnin=0.1, bins=15, cmin=int(0.0015 * n_draws), points=256)
+    cmin = int(0.0015 * n_draws)
+    c = marginals.corner(trace, names=names, select=sel, burnin=0.1, bins=15, cmin=cmin, points=256,
+                         plot2d='hex' if hexagons and len(sel) > 1 else 'hist')
     torch.cuda.synchronize()
     print(f'{g}: corner() of {len(sel)} parameters over {c["n_draws"]} draws in {1e3 * (time.perf_counter() - t0):.1f} ms')
     dens, grid = c['density'].cpu().numpy(), c['grid'].cpu().numpy()
@@ -82,6 +90,14 @@ for g, sel in groups.items():
         for j in range(i + 1, len(sel)):
             print(f'  ({c["names"][i]}, {c["names"][j]}): correlation {float(c["corr"][i, j]):+.3f}, 50 % / 90 % levels {c["levels"][i, j].tolist()}, '
                   f'{int(c["mask"][i, j].sum())} of {15 * 15} cells blanked')
+    hx = c.pop('hex', None)
+    if hx is not None:
+        i, j = hx['pairs'][0].tolist()
+        print(f'  ({c["names"][i]}, {c["names"][j]}) in hexagons, gridsize ({hx["nx"]}, {hx["ny"]}): {int((~hx["mask"][0]).sum())} of '
+              f'{hx["counts"].shape[1]} hold at least cmin = {cmin} draws, 50 % / 90 % levels {hx["levels"][0].tolist()}')
+        for k, v in hx.items():
+            if k not in ('nx', 'ny', 'n_draws'):
+                saved[f'{g}/hex/{k}'] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
     for k, v in c.items():
         if k not in ('names', 'mass', 'n_draws'):
             saved[f'{g}/{k}'] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)

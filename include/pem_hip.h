@@ -895,6 +895,33 @@ int pem_chain_kde_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, 
                           const double* inv_h, const double* scale, double* kde, double* work, size_t work_len,
                           pem_stream_t stream);
 
+/* ---- hexagonal pair bins of a pooled MCMC trace (csrc/pem_hexbin.hip, marginals.hexbins / corner(plot2d='hex'); the pair
+ * panels of uq.ndscatter(..., plot2d='hex') at scripts/pem_v0/mcmc.py:344-385 -- uqtils UNPINNED; the definition is
+ * matplotlib's Axes.hexbin with C=None, linear scales, gridsize=(nx, ny) and extent= given, bit for bit).  x as above: DEVICE,
+ * fp64 [n_rows][ld], n_par <= ld columns used, read in place.
+ *   lattice [n_par][4]     HOST array, {x0, sx, y0, sy} per parameter: with the parameter's extent (lo, hi) and
+ *                          pad = 1e-9 (hi - lo), x0 = lo - pad, sx = ((hi + pad) - x0) / nx, y0 = lo, sy = (hi - lo) / ny
+ *                          (matplotlib pads x only).  Read and checked before the call returns; it travels as a kernel argument.
+ *   counts [P][n_cells]    DEVICE, zeroed by the call; P = n_par (n_par - 1) / 2 pairs (i, j), i < j, in the order (0,1), (0,2)
+ *                          ... (n_par-2, n_par-1), parameter i the x and j the y coordinate; n_cells = (nx+1)(ny+1) + nx ny
+ * A draw (x, y) of a pair, every operation rounded once and none contracted:
+ *   ix = (x - x0_i) / sx_i,  iy = (y - y0_j) / sy_j;  r1 = rint(ix) (half to even), s1 = rint(iy), r2 = floor(ix), s2 = floor(iy)
+ *   d1 = (ix - r1)^2 + 3.0 (iy - s1)^2,  d2 = (ix - r2 - 0.5)^2 + 3.0 (iy - s2 - 0.5)^2
+ *   d1 <  d2: counted in cell r1 (ny+1) + s1                  iff 0 <= r1 <= nx and 0 <= s1 <= ny
+ *   else    : counted in cell (nx+1)(ny+1) + r2 ny + s2       iff 0 <= r2 <  nx and 0 <= s2 <  ny     (ties: second lattice)
+ * The range tests are made on the floating-point r, s: a draw outside the lattice, NaN or +-inf in either coordinate is
+ * dropped from that pair only.  Exact 64-bit counts (integer adds: the same for every run and whichever other parameters
+ * the call holds).  Cell k < (nx+1)(ny+1) has its centre at (x0 + (k / (ny+1)) sx, y0 + (k % (ny+1)) sy); cell
+ * (nx+1)(ny+1) + k at (x0 + (k / ny + 0.5) sx, y0 + (k % ny + 0.5) sy): matplotlib's get_offsets() order.
+ * Refused with PEM_ERR_INVALID_ARG before any device call: a zero size, n_par outside 2 ... PEM_MARGINALS_MAX_PAR, nx or ny
+ * outside 1 ... PEM_HEX_MAX_GRID, ld < n_par, a null pointer, a lattice entry that is not finite, sx or sy not positive,
+ * n_rows beyond one launch (a workgroup's 32-bit tables must see fewer than 2^32 rows; the launch has floor(1024 / task
+ * blocks) row blocks of PEM_HEX_ROW_TILE-row tiles, task blocks = ceil(P / min(256, floor(9216 / n_cells)))).           */
+#define PEM_HEX_MAX_GRID 64
+#define PEM_HEX_ROW_TILE 128
+int pem_chain_hex_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, int nx, int ny, const double* lattice,
+                          uint64_t* counts, pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
