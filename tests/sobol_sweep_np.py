@@ -35,39 +35,59 @@ def model(group, x, torr2pa, uion=None):
     return {'T': th['T'], 'uion': u[:, c], 'v_exh': th['v_exh']}
 
 
-def design(group, n, seed, pressures, p, row, torr2pa, spike=200.0, max_attempts=64):
-    """Row `row` (0: A, 1: B) of `group` at pressure index p: [15][n] and the number of rejected draws."""
+def design_rows(group, n, seed, pressures, p, row, torr2pa, spike=200.0, max_attempts=64, tables=None):
+    """Row `row` (0: A, 1: B) of `group` at pressure index p: [15][n], the rejected draws of every sample (n,) and whether the
+    sample was never accepted (n,): its last draw, attempt max_attempts - 1, is kept.  tables: explicit (kind, a, b) [P][15] tables
+    in the place of the study's (P pressures in the stream numbering); an input the group does not vary is the pin a[c], as the
+    kernel reads it."""
     from oracle import sampler_np
     from hallthrusterpem_amd import sobol as study
     g = study.GROUPS.index(group)
-    kind, a, b = (t[p] for t in study.prior_tables(pressures, group))
-    draw = lambda k: sampler_np.sample(n, 0, seed, study.row_stream(g, len(pressures), p, k, row), kind, a, b)   # noqa: E731
+    n_p = len(pressures) if tables is None else len(tables[0])
+    kind, a, b = (t[p] for t in (study.prior_tables(pressures, group) if tables is None else tables))
+
+    def draw(k):
+        x = sampler_np.sample(n, 0, seed, study.row_stream(g, n_p, p, k, row), kind, a, b)
+        if tables is not None:
+            for c, name in enumerate(study.PEM_V0_NOMINAL):
+                if name not in study.GROUP_INPUTS[group]:
+                    x[c] = a[c]
+        return x
     x = draw(0)
+    rejected = np.zeros(n, dtype=np.int64)
     if group != 'Plume':
-        return x, 0
+        return x, rejected, np.zeros(n, dtype=bool)
     pending = (model(group, x, torr2pa)['profile'] >= spike).any(axis=1)        # sobol.py:61-62
-    rejected = int(pending.sum())
+    rejected += pending
     for k in range(1, max_attempts):
         if not pending.any():
             break
         xk = draw(k)[:, pending]
         x[:, pending] = xk
         hit = (model(group, xk, torr2pa)['profile'] >= spike).any(axis=1)
-        rejected += int(hit.sum())
         idx = np.flatnonzero(pending)
+        rejected[idx[hit]] += 1
         pending[idx[~hit]] = False
-    return x, rejected
+    return x, rejected, pending
 
 
-def sweep(n, seed, pressures, group, torr2pa, uion=None, spike=200.0, clip_percentile=99.0):
-    """Per pressure: {qoi: estimates}, plus for the Plume group the clip threshold and rejected draws."""
+def design(group, n, seed, pressures, p, row, torr2pa, spike=200.0, max_attempts=64, tables=None):
+    """Row `row` (0: A, 1: B) of `group` at pressure index p: [15][n], the number of rejected draws and the number of samples never
+    accepted within max_attempts draws (see design_rows)."""
+    x, rejected, unaccepted = design_rows(group, n, seed, pressures, p, row, torr2pa, spike, max_attempts, tables)
+    return x, int(rejected.sum()), int(unaccepted.sum())
+
+
+def sweep(n, seed, pressures, group, torr2pa, uion=None, spike=200.0, clip_percentile=99.0, max_attempts=64, tables=None):
+    """Per pressure: {qoi: estimates}, plus for the Plume group the clip threshold, the rejected draws and the rows never accepted.
+    tables: see design_rows (pressures then only counts the tables)."""
     from hallthrusterpem_amd import sobol as study
     names = study.GROUP_INPUTS[group]
     cols = [list(study.PEM_V0_NOMINAL).index(k) for k in names]
     out = []
-    for p in range(len(pressures)):
-        xa, ra = design(group, n, seed, pressures, p, 0, torr2pa, spike)
-        xb, rb = design(group, n, seed, pressures, p, 1, torr2pa, spike)
+    for p in range(len(pressures) if tables is None else len(tables[0])):
+        xa, ra, ua = design(group, n, seed, pressures, p, 0, torr2pa, spike, max_attempts, tables)
+        xb, rb, ub = design(group, n, seed, pressures, p, 1, torr2pa, spike, max_attempts, tables)
         fa, fb = model(group, xa, torr2pa, uion), model(group, xb, torr2pa, uion)
         fab = []
         for c in cols:
@@ -81,7 +101,7 @@ def sweep(n, seed, pressures, group, torr2pa, uion=None, spike=200.0, clip_perce
             clip = lambda v: np.where(v > thr, thr, v)                      # noqa: E731
             for d in [fa, fb] + fab:
                 d['jion'] = clip(d['jion'])
-            rec['clip'], rec['rejected'] = thr, ra + rb
+            rec['clip'], rec['rejected'], rec['unaccepted'] = thr, ra + rb, ua + ub
         for q in qois:
             rec[q] = estimates(fa[q], fb[q], np.stack([d[q] for d in fab]))
         out.append(rec)
