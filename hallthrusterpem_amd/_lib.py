@@ -116,6 +116,10 @@ SIGNATURES = {
     'pem_coupled_f32_dev': (C.c_int, [_sz, C.c_float, C.c_float, _dp, _sz, _dp, _sz, _dp, _dp]),
     'pem_saltelli_f32_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, C.c_float, C.c_float, _dp, _dp, C.c_int, _dp]),
     'pem_saltelli_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, _dp]),
+    'pem_saltelli_qmc_f32_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_float, C.c_float, _dp, _dp,
+                                           C.c_int, _dp]),
+    'pem_saltelli_qmc_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp,
+                                           _dp, C.c_int, _dp]),
     'pem_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, _f8, _f8, _f8, _f8, _f8, C.c_int,
                                           _dp, _dp, _dp, _dp, C.c_int, _dp]),
     'pem_chain_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp,
@@ -129,6 +133,8 @@ SIGNATURES = {
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),
+    'pem_sobol_directions': (C.c_int, [C.c_int, _dp]),
+    'pem_sample_sobol_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_chain_autocov_f64_dev': (C.c_int, [_sz, _sz, _sz, _dp] + [_sz] * 6 + [_dp, _dp, _dp, _sz, _dp]),
     'pem_chain_hist_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, C.c_int, _dp] + [_dp] * 4 + [_dp]),
     'pem_chain_kde_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, _sz, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),

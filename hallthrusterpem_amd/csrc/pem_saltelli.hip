@@ -24,6 +24,7 @@
 #include "pem_model.h"
 #include "pem_model_f32.h"
 #include "pem_philox.h"
+#include "pem_qmc.h"
 #include "pem_wave.h"
 
 namespace {
@@ -49,6 +50,7 @@ struct Eval {                // what the estimator needs from one evaluation
 struct Model32 {
     using real = float;
     static constexpr int LDS_BYTES = pem_model32::LDS_FLOATS * 4;
+    static constexpr int QMC_WAVES = 4;          // waves per SIMD saltelli_qmc_kernel is compiled for
     pem_model32::Tab32 t;
     float k, rad, inv_r2, inv_2pi_r2;
     __device__ void stage(void* lds, int tid, int nthreads, double torr2pa, double radius) {
@@ -88,6 +90,7 @@ struct Model64 {
     using real = double;
     static constexpr int QPOLY_DOUBLES = (PEM_NDI + PEM_NQB) * PEM_NDC * 2;
     static constexpr int LDS_BYTES = (PEM_NDI * PEM_NDC + QPOLY_DOUBLES + 2 * 96) * 8;
+    static constexpr int QMC_WAVES = 2;
     const double* dpoly;
     const double2* qpoly;
     const double2* simpson;
@@ -169,15 +172,34 @@ __device__ __forceinline__ void design_row(const SaltelliArg& s, const int* lds_
     }
 }
 
+// the same row from the shifted Sobol' sequence (csrc/pem_qmc.h): input c is sequence dimension `dim0` + c (row A: 0, row B: NIN),
+// bit-identical to pem_sample_sobol_f64_dev.  `gray_lane`: the Gray code of the lane's index; `wave_part`: lane l < 2 NIN holds the
+// fold of the wave's upper Gray-code bits for sequence dimension l, and its shift (pem::qmc_wave_part)
+template <class real>
+__device__ __forceinline__ void design_row_qmc(const int* lds_kind, const double* lds_ab, unsigned int gray_lane, unsigned int wave_part,
+                                               int dim0, real (&x)[NIN]) {
+#pragma unroll
+    for (int d = 0; d < NIN; ++d) {
+        const int kd = __builtin_amdgcn_readfirstlane(lds_kind[d]);
+        const unsigned int p = __builtin_amdgcn_readlane(wave_part, dim0 + d) ^ pem::qmc_lane_part(gray_lane, dim0 + d);
+        x[d] = (real)transform_call_s(kd, lds_ab[2 * d], lds_ab[2 * d + 1], pem::qmc_uniform(p));
+    }
+}
+
+struct QmcShifts {           // the digital shift of each of the 2 NIN sequence dimensions (zeros: the unshifted sequence)
+    unsigned int s[2 * NIN];
+};
+
 // partial: [gridDim.x][2 + 2 nv][NQ]: rows 0,1 = sum fA + fB, sum fA^2 + fB^2; rows 2+2j, 3+2j = sum fB (fAB_j - fA),
 // sum (fA - fAB_j)^2 for varied input j.  flags: [gridDim.x][2] = non-physical thruster results (T < 0 or I_B0 < 0,
 // thruster.py:490-493) and invalid plume samples among all evaluations.
 // One model body, a rolled loop over the nv + 2 evaluations of a base sample (A, B, then A with one column of B); a lane
 // carries two design rows and one evaluation, not 2 (nv + 1) x 3 running sums.
-template <class Model>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))   // two waves per SIMD: <= 256 registers (the fp64 model takes 277 unconstrained)
-void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
-                                                       double* __restrict__ partial, uint64_t* __restrict__ flags) {
+// `shift` != nullptr (a compile-time choice, QMC): the rows come from the Sobol' sequence.  The grid then walks 64-aligned groups of
+// the global index (the first s.first % 64 lanes of the first group are not live), which makes the upper Gray-code bits wave-uniform.
+template <class Model, bool QMC>
+__device__ __forceinline__ void saltelli_body(long long n, const SaltelliArg& s, const unsigned int* shift, double torr2pa, double radius,
+                                              double* __restrict__ partial, uint64_t* __restrict__ flags) {
     using real = typename Model::real;
     __shared__ __attribute__((aligned(16))) unsigned char lds_model[Model::LDS_BYTES];
     __shared__ int lds_kind[NIN + 1], lds_varied[NIN + 1];
@@ -205,21 +227,31 @@ void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
     // every wave runs the same number of iterations (the reductions inside need all 64 lanes): lanes past n evaluate
     // the last sample and contribute zeros
     const long long stride = (long long)gridDim.x * 256;
-    const long long iters = (n + stride - 1) / stride;
+    const long long lead = QMC ? (long long)(s.first & 63ull) : 0;
+    const long long iters = (n + lead + stride - 1) / stride;
     for (long long it = 0; it < iters; ++it) {
-        const long long i = it * stride + (long long)blockIdx.x * 256 + threadIdx.x;
-        const bool live = i < n;
-        const unsigned long long g = s.first + (unsigned long long)(live ? i : n - 1);
+        const long long i = it * stride + (long long)blockIdx.x * 256 + threadIdx.x - lead;
+        const bool live = QMC ? (i >= 0 && i < n) : i < n;
+        // (QMC: a lane that is not live evaluates the point of its own index, whatever that is: every point is a valid input)
+        const unsigned long long g = s.first + (unsigned long long)(QMC || live ? i : n - 1);
+        unsigned int gray_lane = 0, wave_part = 0;
+        if (QMC) {               // (every lane of the wave is here, live or not)
+            const unsigned int gw = (unsigned int)g & ~63u;
+            gray_lane = (unsigned int)g ^ ((unsigned int)g >> 1);
+            if (lane < 2 * NIN) wave_part = pem::qmc_wave_part(gw ^ (gw >> 1), lane) ^ shift[lane];
+        }
         real xa[NIN];
         {
             real xb[NIN];
-            design_row(s, lds_kind, lds_ab, g, s.stream + 1u, xb);
+            if (QMC) design_row_qmc(lds_kind, lds_ab, gray_lane, wave_part, NIN, xb);
+            else design_row(s, lds_kind, lds_ab, g, s.stream + 1u, xb);
 #pragma unroll
             for (int c = 0; c < NIN; ++c) xb_lds[c][threadIdx.x] = xb[c];     // read back by this lane only: no barrier
             // (a compiler barrier: without it the stores are forwarded to the loads below and row B is back in registers)
             asm volatile("" ::: "memory");
         }
-        design_row(s, lds_kind, lds_ab, g, s.stream, xa);
+        if (QMC) design_row_qmc(lds_kind, lds_ab, gray_lane, wave_part, 0, xa);
+        else design_row(s, lds_kind, lds_ab, g, s.stream, xa);
         double fa[NQ] = {0.0, 0.0, 0.0}, fb[NQ] = {0.0, 0.0, 0.0};
         for (int e = 0; e < nv + 2; ++e) {                    // 0: A, 1: B, 2 + j: A with column varied[j] from B
             const int d = e >= 2 ? __builtin_amdgcn_readfirstlane(lds_varied[e - 2]) : -1;
@@ -280,12 +312,28 @@ void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
 }
 
 template <class Model>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))   // two waves per SIMD: <= 256 registers (the fp64 model takes 277 unconstrained)
+void saltelli_kernel(long long n, SaltelliArg s, double torr2pa, double radius,
+                                                       double* __restrict__ partial, uint64_t* __restrict__ flags) {
+    saltelli_body<Model, false>(n, s, nullptr, torr2pa, radius, partial, flags);
+}
+
+template <class Model>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Model::QMC_WAVES)))   // fp32: held to the four waves of the Monte-Carlo launch (130 registers unconstrained)
+void saltelli_qmc_kernel(long long n, SaltelliArg s, QmcShifts shifts, double torr2pa, double radius,
+                         double* __restrict__ partial, uint64_t* __restrict__ flags) {
+    saltelli_body<Model, true>(n, s, shifts.s, torr2pa, radius, partial, flags);
+}
+
+template <class Model, bool QMC = false>
 int launch(const char* who, size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind,
            const double* a, const double* b, int n_varied, const int32_t* varied, double torr2pa, double radius, double* partial,
-           uint64_t* flags, int n_blocks, pem_stream_t stream) {
+           uint64_t* flags, int n_blocks, pem_stream_t stream, int scramble = 0) {
     if (!kind || !a || !b || !varied || !partial || !flags) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL array", who);
     if (n_varied < 1 || n_varied > NIN) return pem::fail(PEM_ERR_INVALID_ARG, "%s: 1 <= n_varied <= %d", who, NIN);
     if (n_blocks < 1) return pem::fail(PEM_ERR_INVALID_ARG, "%s: n_blocks must be positive", who);
+    if (QMC && (first_index > pem::QMC_MAX_POINTS || n_base > pem::QMC_MAX_POINTS - first_index))
+        return pem::fail(PEM_ERR_INVALID_ARG, "%s: indices exceed the 2^%d points of the sequence", who, PEM_SOBOL_BITS);
     if (int rc = pem::check_device()) return rc;
     if (n_base == 0) {   // an empty shard contributes zero to every sum: the caller adds the partials up whatever n_base was
         HIP_TRY(hipMemsetAsync(partial, 0, (size_t)n_blocks * (2 + 2 * n_varied) * NQ * sizeof(double), static_cast<hipStream_t>(stream)));
@@ -309,8 +357,15 @@ int launch(const char* who, size_t n_base, uint64_t first_index, uint64_t seed, 
         if (varied[j] < 0 || varied[j] >= NIN) return pem::fail(PEM_ERR_INVALID_ARG, "%s: varied[%d] = %d out of range", who, j, varied[j]);
         s.varied[j] = varied[j];
     }
-    hipLaunchKernelGGL(saltelli_kernel<Model>, dim3((unsigned)n_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), (long long)n_base, s,
-                       torr2pa, radius, partial, flags);
+    if (QMC) {
+        QmcShifts shifts;
+        for (int d = 0; d < 2 * NIN; ++d) shifts.s[d] = pem::qmc_shift(seed, stream_id, scramble, d);
+        hipLaunchKernelGGL(saltelli_qmc_kernel<Model>, dim3((unsigned)n_blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           (long long)n_base, s, shifts, torr2pa, radius, partial, flags);
+    } else {
+        hipLaunchKernelGGL(saltelli_kernel<Model>, dim3((unsigned)n_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), (long long)n_base, s,
+                           torr2pa, radius, partial, flags);
+    }
     HIP_TRY(hipGetLastError());
     return PEM_OK;
 }
@@ -331,6 +386,22 @@ int pem_saltelli_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uin
                          double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream) {
     return launch<Model64>("pem_saltelli_f64", n_base, first_index, seed, stream_id, kind, a, b, n_varied, varied, torr2pa, radius,
                            partial, flags, n_blocks, stream);
+}
+
+// the same two launches with rows A and B taken from the shifted Sobol' sequence (sequence dimensions 0..14 and 15..29 of the
+// base sample's point; the numbers of pem_sample_sobol_f64_dev) instead of two Philox streams
+int pem_saltelli_qmc_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble, const int32_t* kind,
+                             const double* a, const double* b, int n_varied, const int32_t* varied, float torr2pa, float radius,
+                             double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream) {
+    return launch<Model32, true>("pem_saltelli_qmc_f32", n_base, first_index, seed, stream_id, kind, a, b, n_varied, varied, torr2pa,
+                                 radius, partial, flags, n_blocks, stream, scramble);
+}
+
+int pem_saltelli_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble, const int32_t* kind,
+                             const double* a, const double* b, int n_varied, const int32_t* varied, double torr2pa, double radius,
+                             double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream) {
+    return launch<Model64, true>("pem_saltelli_qmc_f64", n_base, first_index, seed, stream_id, kind, a, b, n_varied, varied, torr2pa,
+                                 radius, partial, flags, n_blocks, stream, scramble);
 }
 
 }  // extern "C"

@@ -215,6 +215,9 @@ def forward_uq(n: int, seed: int = 0, method: str = 'mc', profile: bool = False,
     Draws global samples [0, n) of the counter-based design (this rank evaluates its contiguous shard), evaluates
     them and returns per-sample QoIs of the shard as CUDA tensors:
     `V_cc, div_angle, T_c, I_B0, T, invalid`, the inputs `x` ([15][n_local]) and, if `keep_profile`, `j_ion`.
+    `method`: 'mc' independent draws (generated inside the evaluation launch), 'lhs' a Latin hypercube over n strata, 'sobol' the
+    first n points of the shifted Sobol' sequence (`Design.fill`; n <= 2^30) -- the last two write the inputs with the sampler and
+    evaluate them with the batch launch.  The fused paths (`CoupledBatch.run_mc`, `forward_uq_statistics`) stay Monte-Carlo.
     `batch_size` (default: the whole shard in ONE launch; 1e7 samples with the profile: 1.51 ms against 1.61 in launches of 2^21
     and 1.80 of 2^20, without it 0.66 / 0.70 / 0.77 -- every launch pays its own ramp and tail, tools/forward_uq_batch_probe.py)
     cuts the shard into launches over ranges of the resident batch, e.g. to interleave other work on the stream.
@@ -592,7 +595,8 @@ def train_surrogate(system, fidelity: str = 'multi', **fit_kwargs):
 
 # ------------------------------------------------------------------------------------------- Sobol' indices
 def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed: dict | None = None,
-                  batch_size: int = 1 << 20, device=None, group=None, precision: str = 'fp64', fused: bool | None = None):
+                  batch_size: int = 1 << 20, device=None, group=None, precision: str = 'fp64', fused: bool | None = None,
+                  design: str = 'mc', scramble: bool = True):
     """First-order and total Sobol' indices of scalar QoIs by the Saltelli design: N (d + 2) evaluations for the
     d non-constant inputs (matrices A, B and A with column i from B), `compute_s2=False` as sobol.py:113 asks.
 
@@ -609,12 +613,22 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     partial-sum launches per batch.
     precision='fp32' (BASELINE configs[4]: "fp64 -> fp32 mixed with tolerance check"): the SAME design -- the fp64
     counter-based rows, rounded to float -- through the fp32-arithmetic model.  fp32.compare_with_fp64 is the per-QoI
-    tolerance report of that model."""
+    tolerance report of that model.
+    design='sobol': the matrices A and B are dimensions 0..14 and 15..29 of the first n_base points of the Sobol' sequence
+    (n_base <= 2^30), shifted per dimension by `seed` unless `scramble=False` (csrc/pem_qmc.hip; `Design.fill(method='sobol')`) --
+    for this smooth model first-order indices to 0.01 from 4096 base samples where independent draws leave 0.1 (DESIGN.md
+    section 4.4).  Every path -- fused or not, either precision, sharded over a `group` -- takes either design; the default
+    'mc' is the design of independent Philox draws and changes nothing.  The result carries `design`."""
+    if design not in ('mc', 'sobol'):
+        raise ValueError(f"design must be 'mc' or 'sobol', got '{design}'")
+    if design == 'sobol' and not 0 <= n_base <= sampling.SOBOL_MAX_POINTS:
+        raise ValueError(f"the Sobol' sequence has 2^30 points: n_base = {n_base}")
     import torch
     import torch.distributed as dist
     pri = dict(sampling.PEM_V0_PRIORS if priors is None else priors)
     for k, v in (fixed or {}).items():
         pri[k] = sampling.Prior(sampling.UNIFORM, float(v), float(v), 'fixed')
+    method = design
     design = sampling.Design(priors=pri, seed=seed)
     varied = [i for i, k in enumerate(design.names) if k not in (fixed or {})]
     world = dist.get_world_size(group) if (group is not None or dist.is_initialized()) else 1
@@ -638,7 +652,8 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
         from .fp32 import saltelli_sums
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
         if hi > lo:
-            sums, counts = saltelli_sums(design, varied, hi - lo, first_index=lo, device=dev, precision=precision)
+            sums, counts = saltelli_sums(design, varied, hi - lo, first_index=lo, device=dev, precision=precision, method=method,
+                                         scramble=scramble)
             sums = sums[:, rows]
             acc[0], acc[1], acc[2] = sums[0], sums[1], 2 * (hi - lo)
             acc[3:3 + nd], acc[3 + nd:] = sums[2::2], sums[3::2]
@@ -657,7 +672,11 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     batches, partial, mlast = None, None, -1
 
     def block(b, first, swap):
-        b.run_mc(design, first_index=first, swap_dim=swap)             # Saltelli block generated inside the kernel
+        if method == 'sobol':                                          # the block's rows are written out, then evaluated
+            design.fill(b.inputs, first_index=first, method='sobol', swap_dim=swap, scramble=scramble)
+            b.run()
+        else:
+            b.run_mc(design, first_index=first, swap_dim=swap)         # Saltelli block generated inside the kernel
         return b.qoi if all_rows else b.qoi[rows].contiguous()         # [nq][m]
 
     def sums(slot, fA, fB, fAB, m):
@@ -695,7 +714,7 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     names = [design.names[d] for d in varied]
     res = {'S1': {q: S1[:, i] for i, q in enumerate(qois)}, 'ST': {q: ST[:, i] for i, q in enumerate(qois)},
            'inputs': names, 'mean': {q: mean[i] for i, q in enumerate(qois)}, 'var': {q: var[i] for i, q in enumerate(qois)},
-           'evaluations': int(n_base) * (nd + 2), 'precision': precision, 'fused': fused}
+           'evaluations': int(n_base) * (nd + 2), 'precision': precision, 'fused': fused, 'design': method}
     if counts is not None:
         res['non_physical'], res['invalid'] = int(counts[0]), int(counts[1])
     return res

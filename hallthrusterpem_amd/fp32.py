@@ -93,11 +93,18 @@ def compare_with_fp64(n: int, fill=None, seed: int = 2) -> dict:
 
 
 def saltelli_sums(design, varied, n_base: int, first_index: int = 0, radius: float = 1.0, n_blocks: int | None = None, device=None, stream=None,
-                  precision: str = 'fp32'):
+                  precision: str = 'fp32', method: str = 'mc', scramble: bool = True):
     """One launch of the fused Saltelli design (`pem_saltelli_f32_dev` / `pem_saltelli_f64_dev`, csrc/pem_saltelli.hip): base
     samples first_index .. first_index+n_base-1 of `design` (rows A: its stream, B: stream + 1), `varied` = indices of the
     inputs that get an AB block; `precision` picks the model (fp32 arithmetic on the design rounded to float, or fp64).
+    method='sobol' (`pem_saltelli_qmc_f32_dev` / `pem_saltelli_qmc_f64_dev`): rows A and B are sequence dimensions 0..14 and 15..29
+    of the Sobol' points first_index .. (first_index + n_base <= 2^30), shifted per dimension unless `scramble=False` -- the numbers
+    of `design.fill(method='sobol', swap_dim=-1 / -2)`.  (The keyword is `method`, as in `Design.fill`: `design` is the first argument.)
     Returns (sums [2 + 2 nv][3] float64 CUDA tensor, flags [2] int64: non-physical thruster results, invalid plume samples)."""
+    if method not in ('mc', 'sobol'):
+        raise ValueError(f"saltelli_sums: method must be 'mc' or 'sobol', got '{method}'")
+    if method == 'sobol' and (first_index < 0 or first_index + n_base > 1 << 30):
+        raise ValueError(f"the Sobol' sequence has 2^30 points: first_index + n_base = {first_index + n_base}")
     import torch
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -112,8 +119,13 @@ def saltelli_sums(design, varied, n_base: int, first_index: int = 0, radius: flo
     flags = torch.empty((n_blocks, 2), dtype=torch.int64, device=dev)
     ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                               # noqa: E731
     with torch.cuda.device(dev):
-        fn = _lib.load().pem_saltelli_f32_dev if precision == 'fp32' else _lib.load().pem_saltelli_f64_dev
-        _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, ptr(design.kind), ptr(design.a), ptr(design.b), nv,
-                      ptr(varied), constants.TORR_2_PA, float(radius), C.c_void_p(partial.data_ptr()), C.c_void_p(flags.data_ptr()),
-                      int(n_blocks), C.c_void_p(s.cuda_stream)))
+        lib = _lib.load()
+        tail = (ptr(design.kind), ptr(design.a), ptr(design.b), nv, ptr(varied), constants.TORR_2_PA, float(radius),
+                C.c_void_p(partial.data_ptr()), C.c_void_p(flags.data_ptr()), int(n_blocks), C.c_void_p(s.cuda_stream))
+        if method == 'sobol':
+            fn = lib.pem_saltelli_qmc_f32_dev if precision == 'fp32' else lib.pem_saltelli_qmc_f64_dev
+            _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, int(bool(scramble)), *tail))
+        else:
+            fn = lib.pem_saltelli_f32_dev if precision == 'fp32' else lib.pem_saltelli_f64_dev
+            _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, *tail))
     return partial.sum(dim=0), flags.sum(dim=0)

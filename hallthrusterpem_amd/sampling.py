@@ -18,6 +18,7 @@ from . import _lib
 from .models.coupled import COUPLED_INPUTS
 
 UNIFORM, LOGUNIFORM, NORMAL = 0, 1, 2
+SOBOL_MAX_DIM, SOBOL_MAX_POINTS = 32, 1 << 30     # PEM_SAMPLE_MAX_DIM sequence dimensions of 30-bit points (csrc/pem_sobol_seq.h)
 
 
 @dataclass(frozen=True)
@@ -69,11 +70,23 @@ class Design:
         return len(self.names)
 
     def fill(self, out, first_index: int = 0, method: str = 'mc', n_total: int | None = None, swap_dim: int = -1,
-             stream=None):
+             stream=None, scramble: bool = True):
         """Write samples first_index .. first_index + n - 1 into `out` ([ndim][n] float64 CUDA tensor, rows = names).
 
-        method 'mc': independent draws;  'lhs': Latin hypercube over `n_total` strata per dimension.
-        swap_dim (mc only): Saltelli blocks -- -1 matrix A, -2 matrix B, d >= 0 A with column d from B."""
+        method 'mc': independent draws;  'lhs': Latin hypercube over `n_total` strata per dimension;  'sobol': points
+        first_index .. of the Sobol' sequence (30 bits: first_index + n <= 2^30; `n_total` is ignored), with a random digital shift
+        per dimension keyed by (seed, stream) unless `scramble=False` (csrc/pem_qmc.hip).
+        swap_dim (mc and sobol): Saltelli blocks -- -1 matrix A, -2 matrix B, d >= 0 A with column d from B.  For 'sobol' matrix B
+        is sequence dimensions ndim .. 2 ndim - 1 of the same points, so a block needs 2 ndim <= 32."""
+        if method == 'sobol':       # what the library would refuse, refused before a device is touched
+            if not 1 <= self.ndim <= SOBOL_MAX_DIM:
+                raise ValueError(f"method 'sobol' takes 1 to {SOBOL_MAX_DIM} dimensions, got {self.ndim}")
+            if swap_dim != -1 and 2 * self.ndim > SOBOL_MAX_DIM:
+                raise ValueError(f"a Saltelli block of the Sobol' sequence takes 2 ndim <= {SOBOL_MAX_DIM} dimensions, got ndim = {self.ndim}")
+            if not -2 <= swap_dim < self.ndim:
+                raise ValueError(f'swap_dim {swap_dim} out of range')
+            if first_index < 0 or first_index + out.shape[1] > SOBOL_MAX_POINTS:
+                raise ValueError(f"the Sobol' sequence has 2^30 points: first_index + n = {first_index + out.shape[1]}")
         import torch
         lib = _lib.load()
         assert out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and out.shape[0] == self.ndim
@@ -91,6 +104,10 @@ class Design:
                 rc = lib.pem_sample_lhs_f64_dev(n, first_index, int(n_total if n_total is not None else n), self.seed,
                                                 self.stream, self.ndim, ptr(self.kind), ptr(self.a), ptr(self.b),
                                                 C.c_void_p(out.data_ptr()), ld, C.c_void_p(s.cuda_stream))
+            elif method == 'sobol':
+                rc = lib.pem_sample_sobol_f64_dev(n, first_index, self.seed, self.stream, int(bool(scramble)), self.ndim, ptr(self.kind),
+                                                  ptr(self.a), ptr(self.b), swap_dim, C.c_void_p(out.data_ptr()), ld,
+                                                  C.c_void_p(s.cuda_stream))
             else:
                 raise ValueError(f"unknown sampling method '{method}'")
         _lib.check(rc)

@@ -190,6 +190,24 @@ int pem_sample_tiled_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint
                              const int32_t* kind, const double* a, const double* b, int swap_dim, double* out,
                              pem_stream_t stream);
 
+/* The low-discrepancy design (csrc/pem_qmc.hip): a Sobol' sequence with a random digital shift, for the same kind/a/b table.
+ *   x(i, d) = XOR over the set bits j of gray(i) = i ^ (i >> 1) of v[d][j]      (30-bit Joe-Kuo direction numbers, the ones
+ *             torch.quasirandom.SobolEngine and scipy.stats.qmc.Sobol(bits=30) use; left-aligned to bit 29)
+ *   u(i, d) = ((x ^ s_d) + 0.5) 2^-30     the midpoint of the point's cell: exact in fp64, never 0 or 1 (Phi^-1 stays finite);
+ *             for a U(0, 1) prior and scramble == 0 it is SobolEngine's draw + 2^-31, bit for bit
+ *   s_d     = 0 if scramble == 0, else the top 30 bits of the first word of Philox4x32-10 with counter (d, 0, 0x534F424C,
+ *             stream_id) and key seed: one shift per sequence dimension, never a block of a Monte-Carlo or Latin-hypercube stream
+ * out[d][i] = transform_d(u(first_index + i, d)): a pure function of (seed, stream_id, index, dimension), no running state, so any
+ * sharding of a design is the same design.  swap_dim as for pem_sample_f64_dev, with matrix B = sequence dimensions
+ * ndim .. 2 ndim - 1 of the same points (the usual quasi-Monte-Carlo Saltelli construction).
+ * Refused (PEM_ERR_INVALID_ARG) before any device call: ndim outside [1, PEM_SAMPLE_MAX_DIM]; swap_dim != -1 with
+ * 2 ndim > PEM_SAMPLE_MAX_DIM; first_index + n > 2^30 (the sequence has 2^30 points); a NULL array; an unknown kind; ld < n.
+ * pem_sobol_directions copies the 30 direction numbers of dimension dim (0 .. 31) to out30: host only, touches no device.   */
+int pem_sobol_directions(int dim, uint32_t* out30);
+int pem_sample_sobol_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble, int ndim,
+                             const int32_t* kind, const double* a, const double* b, int swap_dim, double* out,
+                             size_t ld, pem_stream_t stream);
+
 /* Predictive checks (scripts/pem_v0/monte_carlo.py:42-60,63-300; hallthrusterpem_amd/predictive.py).
  * pem_predictive_inputs_f64_dev fills the [15][ld] SoA inputs (COUPLED_INPUTS order) of n samples, sample i belonging to
  * condition c = i mod n_cond: every input starts as draw first_index + i of the design (pem_sample_f64_dev's numbers for
@@ -659,6 +677,15 @@ int pem_saltelli_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed, uin
 int pem_saltelli_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind,
                          const double* a, const double* b, int n_varied, const int32_t* varied, double torr2pa,
                          double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+/* The same two launches on the shifted Sobol' design: rows A and B of base sample first_index + i are sequence dimensions
+ * 0..14 and 15..29 of point first_index + i -- the numbers of pem_sample_sobol_f64_dev(ndim = 15, swap_dim = -1 / -2) with the
+ * same seed, stream_id and scramble.  first_index + n_base > 2^30 is refused.  Everything else as above.                  */
+int pem_saltelli_qmc_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                             const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                             float torr2pa, float radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+int pem_saltelli_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                             const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                             double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
 
 /* ---- the Sobol' study over a pressure sweep (csrc/pem_sobol_sweep.hip) --------------------------------------------------
  * scripts/pem_v0/sobol.py:46-118 (compute_indices; uqtils sobol_sa, third-party: parity UNPINNED): per QoI group only the
