@@ -120,6 +120,14 @@ SIGNATURES = {
                                            C.c_int, _dp]),
     'pem_saltelli_qmc_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp,
                                            _dp, C.c_int, _dp]),
+    'pem_saltelli2_f32_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_float, C.c_float, _dp, _dp,
+                                        C.c_int, _dp]),
+    'pem_saltelli2_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, _dp,
+                                        C.c_int, _dp]),
+    'pem_saltelli2_qmc_f32_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_float, C.c_float,
+                                            _dp, _dp, C.c_int, _dp]),
+    'pem_saltelli2_qmc_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double,
+                                            _dp, _dp, C.c_int, _dp]),
     'pem_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, _f8, _f8, _f8, _f8, _f8, C.c_int,
                                           _dp, _dp, _dp, _dp, C.c_int, _dp]),
     'pem_chain_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp,

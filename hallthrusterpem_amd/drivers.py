@@ -596,7 +596,7 @@ def train_surrogate(system, fidelity: str = 'multi', **fit_kwargs):
 # ------------------------------------------------------------------------------------------- Sobol' indices
 def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed: dict | None = None,
                   batch_size: int = 1 << 20, device=None, group=None, precision: str = 'fp64', fused: bool | None = None,
-                  design: str = 'mc', scramble: bool = True):
+                  design: str = 'mc', scramble: bool = True, second_order: bool = False):
     """First-order and total Sobol' indices of scalar QoIs by the Saltelli design: N (d + 2) evaluations for the
     d non-constant inputs (matrices A, B and A with column i from B), `compute_s2=False` as sobol.py:113 asks.
 
@@ -618,11 +618,30 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     (n_base <= 2^30), shifted per dimension by `seed` unless `scramble=False` (csrc/pem_qmc.hip; `Design.fill(method='sobol')`) --
     for this smooth model first-order indices to 0.01 from 4096 base samples where independent draws leave 0.1 (DESIGN.md
     section 4.4).  Every path -- fused or not, either precision, sharded over a `group` -- takes either design; the default
-    'mc' is the design of independent Philox draws and changes nothing.  The result carries `design`."""
+    'mc' is the design of independent Philox draws and changes nothing.  The result carries `design`.
+
+    second_order=True (Saltelli 2002 in SALib's form; `uq.sobol_sa(compute_s2=True)`): N (2 d + 2) evaluations -- also f(BA_j), B
+    with column j from A -- and, with a constant c per QoI and i < j in the order of the varied inputs,
+        D = sum (fA - c)(fB - c)        C_ij = sum (fBA_i - c)(fAB_j - c)        S2_ij = (C_ij - D) / N / Var - S1_i - S1_j
+    with S1, Var and the mean exactly as above.  E[fBA_i + fAB_j - fA - fB] = 0, so any c leaves S2 unbiased; c near the mean takes
+    the mean^2 term out of its variance (same Philox design, 4096 points: largest |S2| 0.25 without c).  c comes from a pilot: the
+    first-order launch (`fp32.saltelli_sums`) with one varied input over the GLOBAL base samples 0 .. min(n_base, 4096) - 1 of the
+    same design, row 0 / (2 n_pilot); every rank of a `group` runs the same pilot, so c does not depend on the sharding.  fused: the
+    pilot, then one launch per shard (`fp32.saltelli2_sums`, csrc/pem_saltelli2.hip), the sums all-reduced (O(d^2 n_qoi) doubles).
+    fused=False (fp64 only) composes the same estimator from `Design.fill` (A, B; AB_j by swap_dim=j; BA_j by a column copy),
+    `CoupledBatch(profile=False)` and torch sums, batch by batch.  The result gains 'S2': {qoi: [d][d]} (symmetric, zero diagonal),
+    'centre': {qoi: c}, and the mirrored estimates the BA blocks give for free, 'S1_mirror' from sum fA (fBA_j - fB) and
+    'ST_mirror' from sum (fB - fBA_j)^2; 'S1' and 'ST' keep their definition and S2 uses 'S1'.  'evaluations' is N (2 d + 2).
+    Second-order indices need the sequence: on the CPU oracle with the operating point fixed (P_b 1e-5, V_a 300, mdot_a 5e-6; 12
+    inputs, seed 11) design='sobol' gives at 4096 / 16384 base points sum S1 = 0.9996 0.9126 0.9232 / 1.0000 0.9129 0.9281 (V_cc,
+    div_angle, T_c), sum S2 = 0.0023 0.0603 0.1109 / -0.0012 0.0623 0.0626 and the largest pair c1 x c3 = 0.043 for div_angle,
+    while independent draws at 4096 points give sum S2 = +0.33 / -1.00 / +1.62: noise.  second_order=False changes nothing."""
     if design not in ('mc', 'sobol'):
         raise ValueError(f"design must be 'mc' or 'sobol', got '{design}'")
     if design == 'sobol' and not 0 <= n_base <= sampling.SOBOL_MAX_POINTS:
         raise ValueError(f"the Sobol' sequence has 2^30 points: n_base = {n_base}")
+    if second_order and precision == 'fp32' and fused is not None and not fused:     # (refused before a device is touched)
+        raise ValueError('the fp32 model exists in the fused launch only')
     import torch
     import torch.distributed as dist
     pri = dict(sampling.PEM_V0_PRIORS if priors is None else priors)
@@ -648,7 +667,29 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     if precision == 'fp32' and not fused:
         raise ValueError('the fp32 model exists in the fused launch only')
     counts = None
-    if fused:
+    acc2, centre = None, None
+    if second_order:
+        from . import fp32 as _fp32
+        n_pilot = min(int(n_base), 4096)
+        centre = np.zeros(3)
+        if n_pilot > 0:                                                # the same pilot on every rank: global samples 0 .. n_pilot - 1
+            pilot, _ = _fp32.saltelli_sums(design, varied[:1], n_pilot, first_index=0, device=dev, precision=precision, method=method,
+                                           scramble=scramble)
+            centre = (pilot[0] / (2 * n_pilot)).cpu().numpy()
+        npairs = nd * (nd - 1) // 2
+        acc2 = torch.zeros((2 * nd + 1 + npairs, nq), dtype=torch.float64, device=dev)   # mirror S1 sums | mirror ST sums | D | C_ij
+    if fused and second_order:
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        if hi > lo:
+            s2, counts = _fp32.saltelli2_sums(design, varied, hi - lo, centre, first_index=lo, device=dev, precision=precision,
+                                              method=method, scramble=scramble)
+            first, mirror = s2['first'][:, rows], s2['mirror'][:, rows]
+            acc[0], acc[1], acc[2] = s2['ab'][0, rows], s2['ab'][1, rows], 2 * (hi - lo)
+            acc[3:3 + nd], acc[3 + nd:] = first[0::2], first[1::2]
+            acc2[:nd], acc2[nd:2 * nd] = mirror[0::2], mirror[1::2]
+            acc2[2 * nd], acc2[2 * nd + 1:] = s2['D'][rows], s2['pairs'][:, rows]
+        lo = hi
+    elif fused:
         from .fp32 import saltelli_sums
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
         if hi > lo:
@@ -658,6 +699,41 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
             acc[0], acc[1], acc[2] = sums[0], sums[1], 2 * (hi - lo)
             acc[3:3 + nd], acc[3 + nd:] = sums[2::2], sums[3::2]
         lo = hi                                                        # nothing left for the block loop below
+    elif second_order:
+        # the composed form: per batch 2 nd + 2 design blocks written out and evaluated, every sum a torch reduction
+        c = torch.as_tensor(centre[rows], dtype=torch.float64, device=dev)[:, None]
+        bA = bB = bX = fAB = None
+        for off in range(lo, hi, bs):
+            m = min(bs, hi - off)
+            if bA is None or bA.n != m:
+                bA, bB, bX = (CoupledBatch(m, device=dev, profile=False, thruster_qoi=False) for _ in range(3))
+                fAB = torch.empty((nd, nq, m), dtype=torch.float64, device=dev)
+            design.fill(bA.inputs, first_index=off, method=method, swap_dim=-1, scramble=scramble)
+            bA.run()
+            design.fill(bB.inputs, first_index=off, method=method, swap_dim=-2, scramble=scramble)
+            bB.run()
+            fA, fB = bA.qoi[rows], bB.qoi[rows]
+            acc[0] += (fA + fB).sum(1)
+            acc[1] += (fA * fA + fB * fB).sum(1)
+            acc[2] += 2 * m
+            acc2[2 * nd] += ((fA - c) * (fB - c)).sum(1)
+            for j, d in enumerate(varied):
+                design.fill(bX.inputs, first_index=off, method=method, swap_dim=d, scramble=scramble)
+                bX.run()
+                fAB[j] = bX.qoi[rows]
+                acc[3 + j] += (fB * (fAB[j] - fA)).sum(1)
+                acc[3 + nd + j] += ((fA - fAB[j]) ** 2).sum(1)
+            p = 2 * nd + 1
+            for i, d in enumerate(varied):
+                bX.inputs.copy_(bB.inputs)
+                bX.inputs[d].copy_(bA.inputs[d])                       # BA_i: B with column d from A
+                bX.run()
+                fBA = bX.qoi[rows]
+                acc2[i] += (fA * (fBA - fB)).sum(1)
+                acc2[nd + i] += ((fB - fBA) ** 2).sum(1)
+                acc2[p:p + nd - 1 - i] += ((fBA - c) * (fAB[i + 1:] - c)).sum(2)
+                p += nd - 1 - i
+        lo = hi
     import ctypes as C
     from . import _lib
     lib = _lib.load()
@@ -705,6 +781,8 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
         dist.all_reduce(acc, group=group)
         if counts is not None:
             dist.all_reduce(counts, group=group)
+        if acc2 is not None:
+            dist.all_reduce(acc2, group=group)
     cnt = acc[2]
     mean = acc[0] / cnt
     var = acc[1] / cnt - mean * mean
@@ -717,6 +795,18 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
            'evaluations': int(n_base) * (nd + 2), 'precision': precision, 'fused': fused, 'design': method}
     if counts is not None:
         res['non_physical'], res['invalid'] = int(counts[0]), int(counts[1])
+    if second_order:
+        S1m, STm = acc2[:nd] / n_tot / var, acc2[nd:2 * nd] / n_tot / (2 * var)
+        iu = torch.triu_indices(nd, nd, 1, device=dev)                 # the pairs i < j, lexicographic: the order of the C_ij rows
+        pair = (acc2[2 * nd + 1:] - acc2[2 * nd]) / n_tot / var - S1[iu[0]] - S1[iu[1]]
+        S2 = torch.zeros((nq, nd, nd), dtype=torch.float64, device=dev)
+        S2[:, iu[0], iu[1]] = pair.T
+        S2[:, iu[1], iu[0]] = pair.T
+        res['S2'] = {q: S2[i] for i, q in enumerate(qois)}
+        res['S1_mirror'] = {q: S1m[:, i] for i, q in enumerate(qois)}
+        res['ST_mirror'] = {q: STm[:, i] for i, q in enumerate(qois)}
+        res['centre'] = {q: torch.as_tensor(centre[r], dtype=torch.float64, device=dev) for q, r in zip(qois, rows)}
+        res['evaluations'] = int(n_base) * (2 * nd + 2)
     return res
 
 

@@ -8,6 +8,8 @@ QoI").  csrc/pem_fp32.hip holds the kernels; this module is the host side:
                         the two kernels' durations
   saltelli_sums         the fused Saltelli design (one launch: design rows, n_varied + 2 evaluations per base sample and
                         the estimator sums); drivers.sobol_indices(..., precision='fp32') is built on it
+  saltelli2_sums        the same design with the BA blocks and the centred pair sums of the second-order indices (one launch,
+                        2 n_varied + 2 evaluations per base sample); drivers.sobol_indices(..., second_order=True) is built on it
 """
 import ctypes as C
 
@@ -129,3 +131,56 @@ def saltelli_sums(design, varied, n_base: int, first_index: int = 0, radius: flo
             fn = lib.pem_saltelli_f32_dev if precision == 'fp32' else lib.pem_saltelli_f64_dev
             _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, *tail))
     return partial.sum(dim=0), flags.sum(dim=0)
+
+
+def saltelli2_rows(nv: int) -> int:
+    """rows of the second-order partial: 2 statistics, 2 nv first-order, 2 nv mirror, D and nv (nv - 1) / 2 pairs"""
+    return 3 + 4 * nv + nv * (nv - 1) // 2
+
+
+def saltelli2_sums(design, varied, n_base: int, centre, first_index: int = 0, radius: float = 1.0, n_blocks: int | None = None, device=None,
+                   stream=None, precision: str = 'fp64', method: str = 'mc', scramble: bool = True):
+    """One launch of the fused Saltelli design with second-order terms (`pem_saltelli2_f64_dev` / `_f32_dev` / `_qmc_f64_dev` /
+    `_qmc_f32_dev`, csrc/pem_saltelli2.hip): the base samples, rows and models of `saltelli_sums`, evaluated on A, B, AB_j and BA_j
+    (B with column varied[j] from A) -- n_base (2 nv + 2) evaluations.  `centre`: 3 numbers c (V_cc, div_angle, T_c) subtracted from
+    the factors of D and of the pair sums; any constant leaves the estimator unbiased, one near the mean keeps its variance small
+    (drivers.sobol_indices takes it from a pilot).  Returns ({'ab': [2][3] sum fA + fB, sum fA^2 + fB^2;  'first': [2 nv][3], rows
+    2 j, 2 j + 1 = sum fB (fAB_j - fA), sum (fA - fAB_j)^2 -- the rows of `saltelli_sums`;  'mirror': [2 nv][3] = sum fA (fBA_j - fB),
+    sum (fB - fBA_j)^2;  'D': [3] = sum (fA - c)(fB - c);  'pairs': [nv (nv - 1) / 2][3] = sum (fBA_i - c)(fAB_j - c) for i < j in
+    the order of `varied`, pairs in lexicographic order}, flags [2] int64 over all evaluations); float64 CUDA tensors."""
+    if method not in ('mc', 'sobol'):
+        raise ValueError(f"saltelli2_sums: method must be 'mc' or 'sobol', got '{method}'")
+    if method == 'sobol' and (first_index < 0 or first_index + n_base > 1 << 30):
+        raise ValueError(f"the Sobol' sequence has 2^30 points: first_index + n_base = {first_index + n_base}")
+    if centre is None:
+        raise ValueError('saltelli2_sums: centre is required (3 numbers: V_cc, div_angle, T_c)')
+    centre = np.ascontiguousarray([float(v) for v in centre], dtype=np.float64)
+    if centre.shape != (len(QOI_NAMES),):
+        raise ValueError(f'saltelli2_sums: centre holds one number per QoI {QOI_NAMES}, got {centre.size}')
+    import torch
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    s = torch.cuda.current_stream(dev) if stream is None else stream
+    varied = np.ascontiguousarray(varied, dtype=np.int32)
+    nv = int(varied.size)
+    if n_blocks is None:
+        # the grids of `saltelli_sums` (one workgroup per CU is resident: two to eight passes over the CUs); with them the rows both
+        # launches have are the same sums in the same order
+        n_blocks = 512 if precision != 'fp32' else 2048
+    partial = torch.empty((n_blocks, saltelli2_rows(nv), len(QOI_NAMES)), dtype=torch.float64, device=dev)
+    flags = torch.empty((n_blocks, 2), dtype=torch.int64, device=dev)
+    ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                               # noqa: E731
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        tail = (ptr(design.kind), ptr(design.a), ptr(design.b), nv, ptr(varied), ptr(centre), constants.TORR_2_PA, float(radius),
+                C.c_void_p(partial.data_ptr()), C.c_void_p(flags.data_ptr()), int(n_blocks), C.c_void_p(s.cuda_stream))
+        if method == 'sobol':
+            fn = lib.pem_saltelli2_qmc_f32_dev if precision == 'fp32' else lib.pem_saltelli2_qmc_f64_dev
+            _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, int(bool(scramble)), *tail))
+        else:
+            fn = lib.pem_saltelli2_f32_dev if precision == 'fp32' else lib.pem_saltelli2_f64_dev
+            _lib.check(fn(int(n_base), int(first_index), design.seed, design.stream, *tail))
+    # the rows `saltelli_sums` has are added up over the workgroups as it adds them -- a tensor of its partial's shape and strides --
+    # so that the same grid gives the same bits: how torch orders a reduction depends on the shape it reduces
+    head = partial[:, :2 + 2 * nv].contiguous().sum(dim=0)
+    rows = partial[:, 2 + 2 * nv:].sum(dim=0)
+    return ({'ab': head[:2], 'first': head[2:], 'mirror': rows[:2 * nv], 'D': rows[2 * nv], 'pairs': rows[1 + 2 * nv:]}, flags.sum(dim=0))

@@ -686,6 +686,27 @@ int pem_saltelli_qmc_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed,
 int pem_saltelli_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
                              const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
                              double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+/* The Saltelli (2002) extension to second-order indices, one launch (csrc/pem_saltelli2.hip): the arguments of the four launches
+ * above plus `centre`, 3 host doubles c (V_cc, div_angle, T_c; copied into the launch).  Per base sample the model also runs on
+ * B with column varied[j] from A (BA_j): n_base (2 n_varied + 2) evaluations, which `flags` counts over.
+ * partial[n_blocks][rows][3], rows = 3 + 4 nv + nv (nv - 1) / 2 with nv = n_varied:
+ *   0, 1: sum fA+fB, sum fA^2+fB^2;  2+2j, 3+2j: sum fB (fAB_j-fA), sum (fA-fAB_j)^2 (the rows of the launches above);
+ *   2+2nv+2j, 3+2nv+2j: the mirrored sums, sum fA (fBA_j-fB), sum (fB-fBA_j)^2;  2+4nv: D = sum (fA-c)(fB-c);
+ *   3+4nv+p: C_ij = sum (fBA_i-c)(fAB_j-c) for the pairs i < j < nv of `varied` in lexicographic order.                      */
+int pem_saltelli2_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind,
+                          const double* a, const double* b, int n_varied, const int32_t* varied, const double* centre,
+                          float torr2pa, float radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+int pem_saltelli2_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind,
+                          const double* a, const double* b, int n_varied, const int32_t* varied, const double* centre,
+                          double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+int pem_saltelli2_qmc_f32_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                              const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                              const double* centre, float torr2pa, float radius, double* partial, uint64_t* flags, int n_blocks,
+                              pem_stream_t stream);
+int pem_saltelli2_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                              const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                              const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks,
+                              pem_stream_t stream);
 
 /* ---- the Sobol' study over a pressure sweep (csrc/pem_sobol_sweep.hip) --------------------------------------------------
  * scripts/pem_v0/sobol.py:46-118 (compute_indices; uqtils sobol_sa, third-party: parity UNPINNED): per QoI group only the
