@@ -8,7 +8,12 @@ Restates the steps of scripts/pem_v0/mcmc.py that come before `run_mcmc`:
     run_mle(optimizer='nelder-mead') mcmc.py:170-231   `NelderMead`: scipy's bounded, adaptive Nelder-Mead (the default) for S
                                                        simplices at once; the d + 4 points an iteration can ask for are the
                                                        rows of ONE posterior launch, csrc/pem_nm.hip takes the decisions
-    run_laplace / show_laplace       mcmc.py:234-265   `hessian` (central differences, 2 d^2 + 1 points in one call) and
+    run_mle(optimizer='powell')      mcmc.py:170-231   `Powell`: scipy's bounded Powell for S searches at once; a line search wants
+                                                       one value at a time, so one launch of csrc/pem_powell.hip advances every
+                                                       search by one value and the S points are the rows of ONE posterior launch
+    run_mle(optimizer='direct')      mcmc.py:170-231   not restated: scipy's DIRECT is compiled code whose source is not at hand,
+                                                       so it cannot be restated and pinned the way the other three are
+    run_laplace / show_laplace       mcmc.py:234-265  `hessian` (central differences, 2 d^2 + 1 points in one call) and
                                                        `Laplace` (cov = pinv(-H), nearest positive-definite fall-back, draws)
     pdf_slice                        mcmc.py:132-148   `slices`: log prior, likelihood and posterior along every axis
 
@@ -69,11 +74,17 @@ class DifferentialEvolution:
     names, priors: the searched inputs and their priors (the search is over their quantiles).
     mutation: F, or (lo, hi) for F ~ U(lo, hi) drawn once per generation.  seed: the Philox key of every draw.
     The initial population is a Latin hypercube of u (`Design.fill(method='lhs')` over U(0, 1)), as scipy's default init.
+    init: 'lhs' (that default) or 'sobol': the population is `Design.sample(P, method='sobol')` over U(0, 1), the project's
+       shifted Sobol' points.  The reference calls differential_evolution(..., init='sobol'); scipy's own scrambling of the
+       sequence is not reproduced, so the points differ from scipy's.
     use_graph: a generation (the DE launch and f's launches) is one hipGraph replay on one stream."""
 
     def __init__(self, f, names, priors=None, popsize: int = 15, mutation=(0.5, 1.0), recombination: float = 0.7,
                  strategy: str = 'best1bin', tol: float = 0.01, atol: float = 0.0, seed: int = 0, use_graph: bool = False,
-                 device=None):
+                 device=None, init: str = 'lhs'):
+        if init not in ('lhs', 'sobol'):
+            raise ValueError(f"unknown init '{init}' (one of 'lhs', 'sobol')")
+        self.init = init
         self.names = tuple(names)
         self.d = len(self.names)
         if len(set(self.names)) != self.d or self.d < 1:
@@ -102,7 +113,7 @@ class DifferentialEvolution:
         self.state, self.record = z(1, dt=torch.int64), z(3)
         unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
         self.u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(
-            self.P, device=self.device, method='lhs').T.contiguous()
+            self.P, device=self.device, method=self.init).T.contiguous()
         self.history = z(0)
         self._graph = None
 
@@ -362,6 +373,183 @@ class NelderMead:
         return NMResult(theta=self.theta.view(self.S, self.d + 4, self.d)[:, 0].cpu().numpy(), u=sim[:, 0].copy(), value=value,
                         nit=st[:, 1].copy(), nfev=st[:, 2].copy(), converged=st[:, 3] == 1, operations=st[:, 4:9].copy(),
                         best=int(np.argmax(value)), history=self.history[:c + 1].cpu().numpy(), final_simplex=(sim, fsim))
+
+
+# ------------------------------------------------------------------------------------------------------------- Powell
+POWELL_COUNTERS = ('lines', 'golden', 'parabolic', 'rejected', 'off_end', 'tol1', 'clipped', 'extra', 'replaced', 'worse',
+                   'zero_dir', 'zero_disp', 'degenerate', 'one_eval', 'cap')     # state words 8 ... 22 of pem_powell_step_f64_dev
+POWELL_STATUS = {0: 'running', 1: 'ftol met', 2: 'max_iterations reached', 3: 'max_evaluations reached'}
+
+
+@dataclass
+class PowellResult:
+    theta: np.ndarray        # (S, d) scipy's x: the point after the last completed line search of every search
+    u: np.ndarray            # (S, d) in search coordinates
+    value: np.ndarray        # (S,) f there (scipy's -fun); Powell's own value can go down, see best_value
+    nit: np.ndarray          # (S,) completed iterations (scipy's nit)
+    nfev: np.ndarray         # (S,) values consumed (scipy's nfev)
+    converged: np.ndarray    # (S,) bool: the ftol test was met
+    status: np.ndarray       # (S,) 1 the ftol test met, 2 max_iterations reached, 3 stopped by max_evaluations
+    best_theta: np.ndarray   # (S, d) the best point a search has had a value for
+    best_u: np.ndarray       # (S, d)
+    best_value: np.ndarray   # (S,) f there
+    direc: np.ndarray        # (S, d, d) the direction sets the searches end with, in search coordinates
+    counters: dict           # name (POWELL_COUNTERS) -> (S,) how often every branch of the algorithm was taken
+    best: int                # the search of the largest best_value (ties to the lowest index)
+    history: np.ndarray      # (launches, S) best_value after every consumed value
+
+
+class Powell:
+    """scipy's `minimize(method='Powell', bounds=..., options={'xtol': ..., 'ftol': ...})` (run_mle(optimizer='powell'),
+    mcmc.py:170-231), MAXIMISING f, for S independent searches on the device.
+
+    Powell's line searches want one function value at a time.  One launch of `pem_powell_step_f64_dev` (csrc/pem_powell.hip, a
+    workgroup per search) takes the value of the point a search emitted last, advances scipy's algorithm -- the bounded
+    golden-section / parabolic line search, the direction loop, the extrapolated point, the direction replacement -- until
+    the next value is needed and emits that point; the S points are the rows of ONE call of f.  The search runs in the prior's
+    quantile cube, bounded by `search_bounds`; every point, the result, nit and nfev are scipy 1.15's bit for bit wherever
+    scipy is defined (include/pem_hip.h says where it is not).
+
+    f: callable (S, d) float64 device tensor -> S values (`.rows == S`), like `NelderMead`'s: `post.log_posterior` of a posterior
+       built with n_chains = powell.rows, shared_nuisance=True and fresh_nuisance=False.
+    At most one of: x0 (d,) or (S, d) in theta, taken to search coordinates by `quantile` and clipped into the bounds; n_starts
+    Latin-hypercube points of the quantile cube (the `Design` call that makes DE's initial population, keyed by `seed`).  With
+    neither, n_starts = 8.
+    direc: the initial direction set in search coordinates, (d, d) or (S, d, d), one direction per row; the identity if None.
+    use_graph: a step (the launch, f's launches and the copy of the values) is one hipGraph replay on one stream."""
+
+    def __init__(self, f, names, priors=None, x0=None, n_starts=None, direc=None, xtol: float = 1e-4, ftol: float = 1e-4,
+                 seed: int = 0, use_graph: bool = False, device=None):
+        self.names = tuple(names)
+        self.d = d = len(self.names)
+        if len(set(self.names)) != d or d < 1:
+            raise ValueError('names must be distinct and non-empty')
+        if d > _lib.POWELL_MAX_DIM:
+            raise ValueError(f'at most {_lib.POWELL_MAX_DIM} searched inputs (got {d})')
+        if x0 is not None and n_starts is not None:
+            raise ValueError('give at most one of x0 and n_starts')
+        if not (xtol >= 0.0 and ftol >= 0.0):
+            raise ValueError('xtol and ftol must be >= 0')
+        self.kind, self.a, self.b = _table(self.names, priors)
+        self.lb, self.ub = search_bounds(self.names, priors)
+        u0 = None
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if x0.shape != (d,) and (x0.ndim != 2 or x0.shape[1] != d or x0.shape[0] < 1):
+                raise ValueError(f'x0 must have the shape ({d},) or (S, {d})')
+            with np.errstate(invalid='ignore', divide='ignore'):
+                u0 = quantile(x0.reshape(-1, d), self.names, priors)
+            if not np.isfinite(u0).all():
+                raise ValueError('x0 has no finite quantile under the priors (a NaN, or a value <= 0 under a log-uniform prior)')
+            u0 = np.clip(u0, self.lb, self.ub)
+            self.S = u0.shape[0]
+        else:
+            self.S = 8 if n_starts is None else int(n_starts)
+            if self.S < 1:
+                raise ValueError('n_starts must be >= 1')
+        if direc is None:
+            direc0 = np.broadcast_to(np.eye(d), (self.S, d, d))
+        else:
+            direc0 = np.asarray(direc, dtype=np.float64)
+            if direc0.shape != (d, d) and direc0.shape != (self.S, d, d):
+                raise ValueError(f'direc must have the shape ({d}, {d}) or (S, {d}, {d})')
+            if not np.isfinite(direc0).all():
+                raise ValueError('direc must be finite')
+            direc0 = np.broadcast_to(direc0, (self.S, d, d))
+        self.rows = self.S
+        self.f, self.xtol, self.ftol, self.seed, self.use_graph = f, float(xtol), float(ftol), int(seed), bool(use_graph)
+        self._max_iter = 0
+
+        import torch
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if u0 is None:
+            unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
+            u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(self.S, device=self.device, method='lhs').T
+            u0 = np.clip(u0.cpu().numpy(), self.lb, self.ub)
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        self.u0 = torch.as_tensor(np.ascontiguousarray(u0), device=self.device)
+        self.direc0 = torch.as_tensor(np.array(direc0), device=self.device)               # (a copy: broadcast_to's is read-only)
+        self.vec, self.direc, self.scal = z(self.S, _lib.POWELL_VEC_ROWS, d), z(self.S, d, d), z(self.S, _lib.POWELL_SCALARS)
+        self.cand_f, self.theta = z(self.S), z(self.S, d)
+        self.state = z(self.S, _lib.POWELL_STATE_WORDS, dt=torch.int64)
+        self.history = z(0, self.S)
+        self._graph = None
+
+    def _launch(self, finalize: int):
+        """finalize 0: a step; 1: theta = x; 2: theta = best_x"""
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
+        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_powell_step_f64_dev(
+                self.S, self.d, int(finalize), self.xtol, self.ftol, self._max_iter, math.sqrt(2.2e-16),
+                0.5 * (3.0 - math.sqrt(5.0)), ptr(self.kind), ptr(self.a), ptr(self.b), ptr(self.lb), ptr(self.ub), p(self.vec),
+                p(self.direc), p(self.scal), p(self.cand_f), p(self.theta), p(self.state),
+                p(self.history) if self.history.numel() else None, self.history.shape[0],
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _step(self):
+        self._launch(False)
+        self.cand_f.copy_(self.f(self.theta))
+
+    def reset(self):
+        """Back to the starts and the initial directions (the next launch emits the starts)."""
+        self.state.zero_()
+        self.vec[:, 0].copy_(self.u0)
+        self.direc.copy_(self.direc0)
+
+    def _prepare(self, n_launches: int, max_iter: int):
+        """history room for n_launches; the graph is (re)recorded when the history buffer moves or max_iterations changes (it
+        is a kernel argument)"""
+        import torch
+        if self.history.shape[0] < n_launches:
+            self.history = torch.full((n_launches, self.S), math.nan, dtype=torch.float64, device=self.device)
+            self._graph = None
+        if max_iter != self._max_iter:
+            self._max_iter = max_iter
+            self._graph = None
+        if self.use_graph and self._graph is None:
+            self.reset()
+            self._graph, _ = capture_graph(self._step, self.device)
+        self.reset()
+
+    def run(self, max_iterations=None, max_evaluations=None, check_every: int = 50) -> PowellResult:
+        """Search until every start has finished -- the ftol test, or `max_iterations` completed iterations -- or has consumed
+        `max_evaluations` values, then finalize.  scipy's rule for the limits: both None means 1000 d each, one given leaves
+        the other unbounded.  Every running search consumes one value per launch, so a search stopped by `max_evaluations`
+        ends exactly as scipy's does when maxfev interrupts it: theta is the point after the last completed line search.
+        The host reads `state` every `check_every` launches."""
+        import torch
+        if max_iterations is None and max_evaluations is None:
+            max_iterations = max_evaluations = 1000 * self.d
+        if (max_iterations is not None and max_iterations < 1) or (max_evaluations is not None and max_evaluations < 1) \
+                or check_every < 1:
+            raise ValueError('max_iterations >= 1, max_evaluations >= 1 and check_every >= 1')
+        # launch 0 emits the start and consumes nothing.  With max_evaluations unbounded the history keeps the first 1000 d
+        # values (the kernel writes no row past the buffer) and the launches go on until every search has finished.
+        n = None if max_evaluations is None else int(max_evaluations) + 1
+        self._prepare(1000 * self.d + 1 if n is None else n, 0 if max_iterations is None else int(max_iterations))
+        c = 0
+        while n is None or c < n:
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._step()
+            c += 1
+            if c % check_every == 0 and bool((self.state[:, 3] != 0).all().item()):
+                break
+        self._launch(2)                        # theta = every search's best_x, as f saw it
+        best_theta = self.theta.cpu().numpy()
+        self._launch(1)                        # theta = every search's x
+        torch.cuda.synchronize(self.device)
+        st = self.state.cpu().numpy()
+        vec, scal = self.vec.cpu().numpy(), self.scal.cpu().numpy()
+        best_value = scal[:, 19].copy()
+        return PowellResult(theta=self.theta.cpu().numpy(), u=vec[:, 0].copy(), value=-scal[:, 16], nit=st[:, 1].copy(),
+                            nfev=st[:, 2].copy(), converged=st[:, 3] == 1, status=np.where(st[:, 3] == 0, 3, st[:, 3]),
+                            best_theta=best_theta, best_u=vec[:, 4].copy(), best_value=best_value, direc=self.direc.cpu().numpy(),
+                            counters={k: st[:, 8 + j].copy() for j, k in enumerate(POWELL_COUNTERS)},
+                            best=int(np.argmax(best_value)), history=self.history[:min(c - 1, self.history.shape[0])].cpu().numpy())
 
 
 # ----------------------------------------------------------------------------------------------------------- Laplace

@@ -850,6 +850,71 @@ int pem_nm_step_f64_dev(size_t n_simplex, int ndim, int finalize, double rho, do
                         double* sim, double* fsim, double* cand_x, const double* cand_f, double* theta, uint64_t* state,
                         double* history, size_t history_len, pem_stream_t stream);
 
+/* ---- bounded Powell, many searches, one launch per function value (csrc/pem_powell.hip, optimize.Powell) --------------------
+ * Stands in for minimize(obj_fun, x0, method='Powell', bounds=bds, options={'maxiter': maxfev, 'ftol': tol}) of run_mle
+ * (scripts/pem_v0/mcmc.py:170-231, optimizer='powell'): scipy 1.15's _minimize_powell with its bounded line search
+ * (_linesearch_powell, _line_for_search, _minimize_scalar_bounded) for n_search independent searches of dimension ndim, one
+ * wave64 workgroup each, MAXIMISING f over x in [lb, ub]^ndim (g = -f is minimised; a NaN f is g = +inf).  A launch takes the
+ * value of the point it emitted last, advances the algorithm until the next value is needed, and emits that point.
+ * kind/a/b (the prior table, theta = the prior transform of x, as pem_de_step_f64_dev) and lb/ub are HOST arrays of ndim.
+ * sqrt_eps = sqrt(2.2e-16) and golden_mean = 0.5 (3 - sqrt(5)) as the host rounds them; max_iter 0 is no limit.
+ * DEVICE arrays, S = n_search, d = ndim:
+ *   vec [S][PEM_POWELL_VEC_ROWS][d]  rows 0 x (the point after the last completed line search), 1 x1 (x when the iteration
+ *                                    before ended), 2 p and 3 xi (base and direction of the line search in progress; xi also
+ *                                    keeps the displacement while the extrapolated point is out), 4 best_x, 5 the emitted point
+ *   direc [S][d][d]                  the direction set, one direction per row
+ *   scal [S][PEM_POWELL_SCALARS]     0-14 of _minimize_scalar_bounded: a, b, fulc, nfc, xf, rat, e, fx, ffulc, fnfc, fu, xm, tol1,
+ *                                    tol2, and the alpha emitted last; 15-18 of the outer loop: fx, fval, fx2, delta; 19 best_f,
+ *                                    the largest f consumed (at best_x).  All but best_f are values of g = -f.
+ *   cand_f [S]                       f of the emitted rows, written by the caller between launches;  theta [S][d] those rows
+ *   state [S][PEM_POWELL_STATE_WORDS]  0 launches, 1 nit, 2 nfev, 3 status (0 running, 1 the ftol test met, 2 max_iter reached),
+ *                                    4 phase (0 the value of x0 pending, 1 line search i, 2 the value of the extrapolated point
+ *                                    pending, 3 the extra line search), 5 i, 6 bigind, 7 num (values the line search has had),
+ *                                    8 line searches started, then the counts of 9 golden steps, 10 parabolic steps taken,
+ *                                    11 parabolas rejected, 12 parabolic steps moved off an interval end, 13 steps lengthened to
+ *                                    tol1, 14 extrapolations clipped by a bound (lmax < 1), 15 extra line searches, 16 direction
+ *                                    replacements, 17 line searches that returned a worse value than they started from, 18 zero
+ *                                    directions skipped, 19 all-zero displacements, 20 line bounds with lmax <= lmin, 21 line
+ *                                    searches of one value, 22 line searches ended by the 500-value cap, 23 spare.
+ *                                    The caller zeroes word 0.
+ *   history [history_len][S] or NULL   best_f after launch l >= 1 goes to row l - 1 when l - 1 < history_len
+ * By the launch counter l = state word 0 of a search:
+ *   l == 0  the caller has put x0 (already inside the bounds) into row 0 of vec and the directions into direc.  x0 is copied to
+ *           the other rows of vec and emitted; scal is zeroed (best_f = -inf), words 1-23 are zeroed, l = 1.
+ *   l >= 1, status 0  g = -cand_f (+inf for a NaN); nfev += 1; best_f / best_x take it when l == 1 or g < -best_f.  Then by phase
+ *             0: fval = g; an iteration begins (fx = fval, bigind = 0, delta = 0, i = 0) with line search 0.
+ *             1, 3: the value enters _minimize_scalar_bounded where it waited.  While |xf - xm| > tol2 - (b - a) / 2 and num <
+ *                500 the next alpha is scipy's (parabolic when |e| > tol1 and the parabola is acceptable AND p, q and p / q are
+ *                finite, else golden; moved off an end; lengthened to tol1) and p + alpha xi is emitted.  Otherwise the line
+ *                search is done: x = p + xf xi, fval = its fx; phase 1: delta / bigind, i += 1 and line search i, or the end
+ *                of the iteration; phase 3: when xf xi is not all zero direc[bigind] = direc[d-1], direc[d-1] = xf xi; the next
+ *                iteration begins.
+ *             2: fx2 = g; when fx > fx2 and t < 0 (scipy's t) the extra line search from x along the displacement starts,
+ *                otherwise the next iteration begins.
+ *           A line search starts with p = x and (a, b) = _line_for_search(p, xi) over the non-zero components of xi, (0, 0)
+ *           when b < a or either is not finite, tolerance xatol = (xtol * 100) / 100, and emits p + fulc xi, fulc = a +
+ *           golden_mean (b - a); a zero direction is skipped.  The end of an iteration: nit += 1; status 1 when 2 (fx - fval) <=
+ *           ftol (|fx| + |fval|) + 1e-20, else status 2 when nit >= max_iter, else xi = x - x1, x1 = x and x + min(lmax, 1) xi
+ *           is emitted, lmax of _line_for_search(x, xi), 1 for an all-zero xi (scipy raises there).  Every emitted point, and x,
+ *           is min(max(., lb), ub): rounding can carry p + alpha xi one ulp past a bound.  Products and sums are rounded
+ *           separately.  l += 1.
+ *   l >= 1, status != 0  frozen: the emitted point is x and stays; only l and the history column move.
+ *   finalize 1  consumes nothing: the search's row of theta becomes the transform of x, whose value is fval (exactly what scipy
+ *           returns when maxfev interrupts a line search); l is kept.  finalize 2: the same with best_x, whose value is best_f.
+ *           Nothing happens to a search with l == 0.
+ * No atomics, no communication between workgroups: the same bits on every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: n_search 0, ndim outside [1, PEM_POWELL_MAX_DIM], finalize
+ * outside 0 ... 2, a NULL array other than history, lb > ub, a negative or NaN tolerance, sqrt_eps or golden_mean outside (0, 1), an unknown prior
+ * kind, a history with history_len 0.                                                                                      */
+#define PEM_POWELL_MAX_DIM 32
+#define PEM_POWELL_STATE_WORDS 24
+#define PEM_POWELL_SCALARS 20
+#define PEM_POWELL_VEC_ROWS 6
+int pem_powell_step_f64_dev(size_t n_search, int ndim, int finalize, double xtol, double ftol, uint64_t max_iter, double sqrt_eps,
+                            double golden_mean, const int32_t* kind, const double* a, const double* b, const double* lb,
+                            const double* ub, double* vec, double* direc, double* scal, const double* cand_f, double* theta,
+                            uint64_t* state, double* history, size_t history_len, pem_stream_t stream);
+
 /* ---- delayed-rejection adaptive Metropolis, one launch per step (csrc/pem_dram.hip, calibration.DeviceDRAM) -----------------
  * Stands in for uq.dram(fun, p0, niter, adapt_after, adapt_interval, eps, gamma) of run_mcmc (scripts/pem_v0/mcmc.py:275-300;
  * uqtils is third-party and absent: parity UNPINNED, the algorithm is calibration.DRAM's) for n_chains chains of dimension
