@@ -26,6 +26,7 @@ NM_MAX_DIM, NM_STATE_WORDS = 32, 10   # PEM_NM_MAX_DIM / PEM_NM_STATE_WORDS: dim
 POWELL_MAX_DIM, POWELL_STATE_WORDS = 32, 24   # PEM_POWELL_MAX_DIM / PEM_POWELL_STATE_WORDS: the same of pem_powell_step_f64_dev, per search
 POWELL_SCALARS, POWELL_VEC_ROWS = 20, 6       # PEM_POWELL_SCALARS / PEM_POWELL_VEC_ROWS: its doubles and d-vectors per search
 DRAM_MAX_DIM = 32              # PEM_DRAM_MAX_DIM: dimensions of pem_dram_step_f64_dev (one lane per dimension)
+ENSEMBLE_MAX_DIM, ENSEMBLE_MAX_WALKERS = 32, 1024   # PEM_ENSEMBLE_MAX_DIM / _MAX_WALKERS: dimensions and walkers per ensemble of pem_ensemble_step_f64_dev
 CHAIN_TIME_BLOCK = 4096             # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
 MARGINALS_MAX_PAR, MARGINALS_MAX_BINS = 32, 64   # PEM_MARGINALS_MAX_PAR / _MAX_BINS: parameters and bins of pem_chain_hist_f64_dev
 HIST_ROW_TILE = 128                 # PEM_HIST_ROW_TILE: rows it bins per stage
@@ -141,6 +142,8 @@ SIGNATURES = {
     'pem_powell_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _f8, _f8, C.c_uint64, _f8, _f8] + [_dp] * 12 + [_sz, _dp]),
     'pem_dram_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_uint64, _f8, _f8, C.c_uint64, C.c_uint64, C.c_uint64, _sz, C.c_uint64]
                                         + [_dp] * 13 + [_dp]),
+    'pem_ensemble_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, C.c_uint64, _sz, C.c_uint64]
+                                            + [_dp] * 10 + [_dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

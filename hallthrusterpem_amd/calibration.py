@@ -29,6 +29,8 @@ model's place, j_ion rebuilt from its SVD latents and I_D taken from the surroga
 
 `DRAM` restates the reference's sampler as torch operations around two posterior evaluations per step; `DeviceDRAM` is the same
 algorithm with the sampler's own work in one launch per step (`pem_dram_step_f64_dev`) and both proposals in ONE evaluation.
+`DeviceEnsemble` is the affine-invariant ensemble sampler (stretch and DE moves), which needs no proposal covariance: half an
+ensemble's walkers per evaluation, one launch of `pem_ensemble_step_f64_dev` per half-step.
 """
 import ctypes as C
 import math
@@ -695,3 +697,157 @@ class DeviceDRAM:
     def adaptation_failures(self) -> int:
         """chains that skipped an adaptation because their covariance had a pivot that was not > 0 (`DRAM` would raise there)"""
         return int((self.flags & 1).sum())
+
+
+class DeviceEnsemble:
+    """The affine-invariant ensemble sampler (Goodman & Weare 2010, the algorithm of emcee; third-party and absent here: parity
+    UNPINNED) with the whole sampler on the device: E independent ensembles of K walkers, one launch of
+    `pem_ensemble_step_f64_dev` (csrc/pem_ensemble.hip) per half-step.  It needs NO proposal covariance and behaves identically
+    under any affine change of the parameters, which is what a posterior whose parameters span forty decades asks for.
+
+    An ensemble's walkers are two fixed halves of H = K / 2.  A step moves half 0 against half 1, then half 1 against the new
+    half 0; each launch resolves the half-step whose H proposals were just evaluated and proposes the next, so a step is
+    [log_posterior(prop) ; launch ; log_posterior(prop) ; launch] on one stream, with `use_graph` one hipGraph replay without
+    parallel branches.  Per (ensemble, half-step) the half takes the DE move (ter Braak; y = x + g (x_j1 - x_j2), g = g0 (1 +
+    sigma n), g0 = 2.38 / sqrt(2d) by default) with probability `de_fraction`, otherwise the stretch move of scale `a`
+    (y = x_j + z (x - x_j), z = ((a - 1) u + 1)^2 / a, weight z^(d - 1)).  emcee's random re-split of the halves is not done.
+    The draws are Philox4x32-10 keyed by `seed` (include/pem_hip.h).
+
+    log_posterior: callable on an (E H, d) float64 device tensor returning (E H,) values.  ITS VALUE MUST NOT DEPEND ON THE
+    ROW, as for `DeviceDRAM`: a closed form, or `.log_posterior` of a `SystemPosterior` / `JionPosterior` / `SurrogatePosterior`
+    built with n_chains=E*H, shared_nuisance=True, fresh_nuisance=False.
+
+    theta0: (K, d) starts (n_ensembles == 1) or (E, K, d); K even and >= 2d, as emcee asks.  Every start must have a finite
+    log posterior (they are evaluated half by half through the same call).  `ball` draws starts around a point.  `run`
+    continues across calls.  There is no CPU path.
+
+    Reading the result: the trace is (rows, E, K, d).  THE WALKERS OF ONE ENSEMBLE ARE NOT INDEPENDENT CHAINS -- each moves
+    along lines through the others -- so R-hat and ESS belong on the E ensemble-mean series,
+    `diagnostics.summary(trace.mean(dim=2))`, while `trace.reshape(rows, E * K, d)` is what `marginals` pools."""
+
+    def __init__(self, log_posterior, theta0, n_ensembles: int = 1, seed: int = 0, a: float = 2.0, de_fraction: float = 0.0,
+                 g0: float | None = None, sigma: float = 1e-5, device=None, use_graph: bool = True):
+        import torch
+        if isinstance(theta0, torch.Tensor):
+            if device is None:
+                device = theta0.device
+            theta0 = theta0.detach().cpu().numpy()
+        t0 = np.asarray(theta0, dtype=np.float64)
+        if t0.ndim == 2 and int(n_ensembles) == 1:
+            t0 = t0[None]
+        if t0.ndim != 3 or (int(n_ensembles) not in (1, t0.shape[0])):
+            raise ValueError('theta0 must be (K, d) with n_ensembles == 1, or (E, K, d)')
+        self.E, self.K, self.d = t0.shape
+        if not 1 <= self.d <= _lib.ENSEMBLE_MAX_DIM:
+            raise ValueError(f'DeviceEnsemble samples 1 to {_lib.ENSEMBLE_MAX_DIM} parameters (got {self.d})')
+        if self.E < 1 or self.K % 2 or self.K < 2 * self.d or self.K > _lib.ENSEMBLE_MAX_WALKERS:
+            raise ValueError(f'DeviceEnsemble needs an even number of walkers K with 2 d = {2 * self.d} <= K <= '
+                             f'{_lib.ENSEMBLE_MAX_WALKERS} per ensemble (got {self.K})')
+        if device is not None and torch.device(device).type != 'cuda':
+            raise ValueError(f"DeviceEnsemble runs on the GPU only (got device '{device}')")
+        g0 = 2.38 / math.sqrt(2.0 * self.d) if g0 is None else float(g0)
+        if not (0.0 <= de_fraction <= 1.0):
+            raise ValueError(f'de_fraction must be in [0, 1] (got {de_fraction})')
+        if de_fraction > 0.0 and self.K < 4:
+            raise ValueError('the DE move needs two partners in the other half: K >= 4')
+        if not (a > 1.0 and math.isfinite(a) and g0 > 0.0 and math.isfinite(g0) and sigma >= 0.0 and math.isfinite(sigma)):
+            raise ValueError('need finite a > 1, g0 > 0 and sigma >= 0')
+        self.f, self.seed, self.use_graph = log_posterior, int(seed), bool(use_graph)
+        self.a, self.de_fraction, self.g0, self.sigma = float(a), float(de_fraction), g0, float(sigma)
+        dev = self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        E, K, d = self.E, self.K, self.d
+        H = self.H = K // 2
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=dev)                # noqa: E731
+        self.theta = torch.as_tensor(np.ascontiguousarray(t0), device=dev).clone()
+        self.prop, self.prop_logp, self.log_q = z(E, H, d), z(E, H), z(E, H)
+        self.state, self.accepted = z(E, dt=torch.int64), z(E, K, dt=torch.int64)
+        self.steps = 0
+        self._trace = self._logp_trace = None
+        self._window = (0, 0, 1)                                                             # trace_first, trace_len, thin
+        self._graph, self._graph_key = None, None
+        halves = []
+        for h in (0, 1):                                                                     # the starts, half by half
+            self.prop.copy_(self.theta[:, h * H:(h + 1) * H])
+            halves.append(self.f(self.prop.view(E * H, d)).reshape(E, H).clone())
+        self.logp = torch.cat(halves, dim=1).contiguous()
+        if not bool(torch.isfinite(self.logp).all()):
+            bad = int((~torch.isfinite(self.logp)).sum())
+            raise ValueError(f'{bad} of the {E * K} starts have a log posterior that is not finite: every walker must start '
+                             'inside the support')
+        self._launch()                                                                       # launch 0: the proposals of half-step 1
+
+    @staticmethod
+    def ball(center, scale, n_walkers: int, n_ensembles: int = 1, seed: int = 0):
+        """(n_ensembles, n_walkers, d) starts center + scale * N(0, 1) from np.random.default_rng(seed); `scale` a number or
+        one per parameter (a fraction of |center|, the width of a prior).  The final population of
+        `optimize.DifferentialEvolution` and draws from `optimize.Laplace` are natural starts as well: they already have the
+        posterior's shape, and this sampler needs nothing else."""
+        center = np.atleast_1d(np.asarray(center, dtype=np.float64))
+        rng = np.random.default_rng(seed)
+        return center + np.asarray(scale, dtype=np.float64) * rng.standard_normal((int(n_ensembles), int(n_walkers), center.size))
+
+    def _launch(self):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                    # noqa: E731
+        first, length, thin = self._window
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_ensemble_step_f64_dev(
+                self.E, self.K, self.d, self.seed, self.a, self.de_fraction, self.g0, self.sigma, first, length, thin,
+                p(self.theta), p(self.logp), p(self.prop), p(self.prop_logp), p(self.log_q), p(self.state), p(self.accepted),
+                p(self._trace), p(self._logp_trace), None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _step(self):
+        for _ in range(2):
+            self.prop_logp.view(-1).copy_(self.f(self.prop.view(self.E * self.H, self.d)))
+            self._launch()
+
+    def _prepare(self):
+        """the graph is (re)recorded when a trace buffer or the trace window moves: a recorded launch carries them by value.
+        The steps that recording runs are undone."""
+        key = (self._trace.data_ptr() if self._trace is not None else 0,
+               self._logp_trace.data_ptr() if self._logp_trace is not None else 0) + self._window
+        if not self.use_graph or (self._graph is not None and self._graph_key == key):
+            return
+        kept = (self.theta, self.logp, self.prop, self.prop_logp, self.log_q, self.state, self.accepted)
+        saved = [t.clone() for t in kept]
+        self._graph = None                                                                   # (frees the old recording first)
+        self._graph, _ = capture_graph(self._step, self.device)
+        self._graph_key = key
+        for t, s in zip(kept, saved):
+            t.copy_(s)
+
+    def run(self, n_steps: int, keep: bool = True, thin: int = 1, keep_logp: bool = False):
+        """Advance every ensemble n_steps whole steps (each walker is proposed to once per step).  Returns the
+        (ceil(n_steps / thin), E, K, d) trace as a device tensor if `keep` -- steps 1, 1 + thin, ... of this call -- and with
+        `keep_logp` the pair (trace, logp trace (ceil(n_steps / thin), E, K))."""
+        import torch
+        n_steps, thin = int(n_steps), int(thin)
+        if n_steps < 0 or thin < 1:
+            raise ValueError('n_steps >= 0 and thin >= 1')
+        rows = -(-n_steps // thin)
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)              # noqa: E731
+        self._trace = new(rows, self.E, self.K, self.d) if keep and rows else None
+        self._logp_trace = new(rows, self.E, self.K) if keep and keep_logp and rows else None
+        self._window = (self.steps, rows, thin) if self._trace is not None else (0, 0, 1)
+        if n_steps:
+            self._prepare()
+        for _ in range(n_steps):
+            if self.use_graph:
+                self._graph.replay()
+            else:
+                self._step()
+        self.steps += n_steps
+        trace, logp_trace = self._trace, self._logp_trace
+        if keep and trace is None:
+            trace = new(0, self.E, self.K, self.d)
+            logp_trace = new(0, self.E, self.K) if keep_logp else None
+        self._trace = self._logp_trace = None
+        self._window = (0, 0, 1)
+        if not keep:
+            return None
+        return (trace, logp_trace) if keep_logp else trace
+
+    @property
+    def acceptance(self):
+        """(E, K): fraction of its proposals each walker accepted"""
+        return self.accepted.double() / max(1, self.steps)

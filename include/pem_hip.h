@@ -952,6 +952,44 @@ int pem_dram_step_f64_dev(size_t n_chains, int ndim, uint64_t seed, double gamma
                           uint64_t* state, uint64_t* accepted, uint32_t* flags, double* trace, double* logp_trace, double* draws,
                           pem_stream_t stream);
 
+/* ---- affine-invariant ensemble sampler, one launch per half-step (csrc/pem_ensemble.hip, calibration.DeviceEnsemble) --------
+ * Goodman & Weare's stretch move and ter Braak's DE move as emcee runs them (third-party and absent: parity UNPINNED; the
+ * launch is restated in tests/ensemble_np.py) for n_ensembles independent ensembles of n_walkers = K walkers (K even, H = K / 2)
+ * of dimension ndim = d, one workgroup per ensemble.  The halves are fixed: half 0 is walkers [0, H), half 1 walkers [H, K).
+ * Half-step s = 1, 2, ... moves half (s - 1) mod 2 against the other, the complement; two half-steps are a step.  All state is
+ * in DEVICE arrays of the caller:
+ *   theta [E][K][d], logp [E][K]  the walkers and their log posteriors
+ *   prop [E][H][d]                the pending proposals of the half that moves: the caller evaluates the log posterior on prop
+ *   prop_logp [E][H]              seen as (E H, d) and writes the E H values here between two launches
+ *   log_q [E][H]                  log of the proposal weight of each pending proposal (written by the launch that proposed)
+ *   state [E]                     launches seen by the ensemble (the caller zeroes it; a captured graph advances it)
+ *   accepted [E][K]               acceptances per walker
+ *   trace [trace_len][E][K][d], logp_trace [trace_len][E][K]   either may be NULL
+ *   draws NULL or [E][H][6]       per moving walker: move (0 stretch, 1 DE), z or g, j1, j2 (-1: none) and, in column 5, u_move
+ *                                 of the half-step PROPOSED by the launch; in column 4 u_acc of the half-step it RESOLVED
+ * Launch s = state[e].  s == 0: nothing is pending.  s >= 1 resolves half-step s: walker m of the moving half takes its proposal
+ * and prop_logp iff log(u_acc) < log_q + (prop_logp - logp) (a NaN on either side compares false; -inf is never accepted; a
+ * walker at -inf takes any finite value).  When s is even, step t = s / 2 has ended: with r = t - 1 - trace_first the ensemble
+ * goes to row r / thin of the traces when r >= 0, r mod thin == 0 and r / thin < trace_len.  Every launch then proposes
+ * half-step s + 1 from the complement as it now stands, and sets state[e] = s + 1.  One u_move per (ensemble, half-step) picks
+ * the move of the whole half, DE when u_move < de_fraction:
+ *   stretch  z = ((a - 1) u + 1)^2 / a,  y = x_j1 + z (x_w - x_j1),      log_q = (d - 1) log z
+ *   DE       g = g0 (1 + sigma n),        y = x_w + g (x_j1 - x_j2),      log_q = 0
+ * products and sums rounded separately.  Draws: Philox4x32-10(counter = (ensemble, half-step mod 2^32, purpose, m), key = seed),
+ * m the walker's index in its half: purpose 0x454E0000 (m = 0) u_move = u53(x, y); 0x454E0001 j1 = (x H) >> 32, j2 =
+ * (y (H - 1)) >> 32 plus 1 if >= j1, u = u53(z, w) or n = normcdfinv((2k + 1) 2^-53) of the 52-bit k from (z, w); 0x454E0002
+ * u_acc = u53(x, y).  No atomics, no communication between workgroups: the same bits on every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: n_ensembles 0, n_walkers odd or outside
+ * [2, PEM_ENSEMBLE_MAX_WALKERS], de_fraction > 0 with n_walkers < 4, ndim outside [1, PEM_ENSEMBLE_MAX_DIM], a not finite or
+ * not > 1, de_fraction outside [0, 1], g0 not > 0, sigma < 0, either not finite, thin 0, a NULL required array, a trace with
+ * trace_len 0.                                                                                                                 */
+#define PEM_ENSEMBLE_MAX_DIM 32
+#define PEM_ENSEMBLE_MAX_WALKERS 1024
+int pem_ensemble_step_f64_dev(size_t n_ensembles, int n_walkers, int ndim, uint64_t seed, double a, double de_fraction, double g0,
+                              double sigma, uint64_t trace_first, size_t trace_len, uint64_t thin, double* theta, double* logp,
+                              double* prop, const double* prop_logp, double* log_q, uint64_t* state, uint64_t* accepted,
+                              double* trace, double* logp_trace, double* draws, pem_stream_t stream);
+
 /* ---- MCMC chain diagnostics (hallthrusterpem_amd/diagnostics.py; the lag sums of uq.autocorrelation at
  * scripts/pem_v0/mcmc.py:310 -- uqtils, third-party, parity UNPINNED).  x: fp64 [n_rows][ld], unit column stride (a
  * (n, K, d) trace seen as n rows of K*d series; the pointer needs only 8-byte alignment).  Segment s is rows
