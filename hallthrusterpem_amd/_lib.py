@@ -144,6 +144,8 @@ SIGNATURES = {
                                         + [_dp] * 13 + [_dp]),
     'pem_ensemble_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, C.c_uint64, _sz, C.c_uint64]
                                             + [_dp] * 10 + [_dp]),
+    'pem_tempered_ensemble_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, _dp, C.c_uint64, _sz,
+                                                     C.c_uint64] + [_dp] * 15 + [_dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

@@ -31,6 +31,9 @@ model's place, j_ion rebuilt from its SVD latents and I_D taken from the surroga
 algorithm with the sampler's own work in one launch per step (`pem_dram_step_f64_dev`) and both proposals in ONE evaluation.
 `DeviceEnsemble` is the affine-invariant ensemble sampler (stretch and DE moves), which needs no proposal covariance: half an
 ensemble's walkers per evaluation, one launch of `pem_ensemble_step_f64_dev` per half-step.
+`DeviceTemperedEnsemble` is replica exchange over it for a posterior with more than one mode: a ladder of tempered ensembles per
+replica, swaps between neighbouring temperatures inside `pem_tempered_ensemble_step_f64_dev`, the log evidence by thermodynamic
+integration.
 """
 import ctypes as C
 import math
@@ -851,3 +854,243 @@ class DeviceEnsemble:
     def acceptance(self):
         """(E, K): fraction of its proposals each walker accepted"""
         return self.accepted.double() / max(1, self.steps)
+
+
+class DeviceTemperedEnsemble:
+    """Replica exchange (parallel tempering) over `DeviceEnsemble`, for a posterior with more than one mode: R independent
+    replicas of a ladder of T inverse temperatures 1 = beta_0 > beta_1 > ... >= 0, at every (replica, temperature) one ensemble
+    of K walkers that samples prior(x) likelihood(x)^beta_t, E = R T ensembles in all, one launch of
+    `pem_tempered_ensemble_step_f64_dev` (csrc/pem_tempering.hip) per half-step.  ptemcee, which runs this over emcee, is
+    third-party and absent here: parity UNPINNED; the rules are this project's own (include/pem_hip.h) and
+    tests/tempering_np.py restates them.
+
+    The moves are `DeviceEnsemble`'s stretch and DE moves with the same draws, accepted iff
+    log u < log q + (pi' - pi) + beta_t (l' - l); a proposal whose l or pi is not finite is refused at every temperature, beta = 0
+    included.  After the second half-step of step n (n = 1, 2, ...) the pairs (t, t + 1) with t = n mod 2 (mod 2) are visited:
+    walker k of t and walker k of t + 1 exchange places iff log u < (beta_t - beta_{t+1}) (l_{t+1,k} - l_{t,k}).  The hot
+    ensembles cross between modes, the swaps hand their points down, and t = 0 is the posterior itself.  A step is
+    [l(prop), pi(prop) ; launch ; l(prop), pi(prop) ; launch] on one stream, with `use_graph` one hipGraph replay without
+    parallel branches.
+
+    log_likelihood, log_prior: callables on an (E H, d) float64 device tensor (H = K / 2) returning (E H,) values THAT DO NOT
+    DEPEND ON THE ROW: closed forms, or `.log_likelihood` and `.log_prior` of a `SystemPosterior` / `JionPosterior` /
+    `SurrogatePosterior` built with n_chains=E*H, shared_nuisance=True, fresh_nuisance=False.
+
+    betas: the ladder, strictly decreasing from 1, finite, >= 0; None: `ladder(n_temperatures, beta_min, include_prior)`, the
+    geometric ladder from 1 down to beta_min with a final 0 appended when include_prior (thermodynamic integration needs it).
+    theta0: (K, d), (T, K, d) or (R, T, K, d) starts, K even and >= 2d; every start must have a finite l and pi.  `ball` draws
+    starts around a point.  `run` continues across calls.  There is no CPU path.
+
+    Reading the result: the trace is (rows, R, T, K, d) with `loglik_trace` and `logprior_trace` (rows, R, T, K) beside it (the
+    last kept run's).  `cold()` is its t = 0 slice, the posterior's draws; the other temperatures are not.  `swap_rates()` is
+    what a ladder is tuned by: a rate near 0 between two temperatures means they do not talk.  `log_evidence()` integrates the
+    mean log likelihood over beta."""
+
+    def __init__(self, log_likelihood, log_prior, theta0, betas=None, n_temperatures: int = 8, n_replicas: int = 1,
+                 beta_min: float = 1e-2, include_prior: bool = False, seed: int = 0, a: float = 2.0, de_fraction: float = 0.0,
+                 g0: float | None = None, sigma: float = 1e-5, device=None, use_graph: bool = True):
+        import torch
+        if isinstance(theta0, torch.Tensor):
+            if device is None:
+                device = theta0.device
+            theta0 = theta0.detach().cpu().numpy()
+        self.betas = self.ladder(n_temperatures, beta_min, include_prior) if betas is None else self.check_ladder(betas)
+        T, R = self.betas.size, int(n_replicas)
+        t0 = np.asarray(theta0, dtype=np.float64)
+        if R < 1 or t0.ndim not in (2, 3, 4) or (t0.ndim >= 3 and t0.shape[-3] != T) or (t0.ndim == 4 and t0.shape[0] != R):
+            raise ValueError(f'theta0 must be (K, d), (T, K, d) or (R, T, K, d) with T = {T} temperatures and R = n_replicas = {R} '
+                             f'(got {t0.shape})')
+        t0 = np.array(np.broadcast_to(t0, (R, T) + t0.shape[-2:]))
+        self.R, self.T, self.K, self.d = t0.shape
+        self.E = self.R * self.T
+        if not 1 <= self.d <= _lib.ENSEMBLE_MAX_DIM:
+            raise ValueError(f'DeviceTemperedEnsemble samples 1 to {_lib.ENSEMBLE_MAX_DIM} parameters (got {self.d})')
+        if self.K % 2 or self.K < 2 * self.d or self.K > _lib.ENSEMBLE_MAX_WALKERS:
+            raise ValueError(f'DeviceTemperedEnsemble needs an even number of walkers K with 2 d = {2 * self.d} <= K <= '
+                             f'{_lib.ENSEMBLE_MAX_WALKERS} per ensemble (got {self.K})')
+        if not np.isfinite(t0).all():
+            bad = int((~np.isfinite(t0).all(axis=-1)).sum())
+            raise ValueError(f'{bad} of the {self.E * self.K} starts have a coordinate that is not finite')
+        if device is not None and torch.device(device).type != 'cuda':
+            raise ValueError(f"DeviceTemperedEnsemble runs on the GPU only (got device '{device}')")
+        g0 = 2.38 / math.sqrt(2.0 * self.d) if g0 is None else float(g0)
+        if not (0.0 <= de_fraction <= 1.0):
+            raise ValueError(f'de_fraction must be in [0, 1] (got {de_fraction})')
+        if de_fraction > 0.0 and self.K < 4:
+            raise ValueError('the DE move needs two partners in the other half: K >= 4')
+        if not (a > 1.0 and math.isfinite(a) and g0 > 0.0 and math.isfinite(g0) and sigma >= 0.0 and math.isfinite(sigma)):
+            raise ValueError('need finite a > 1, g0 > 0 and sigma >= 0')
+        self.f_lik, self.f_prior, self.seed, self.use_graph = log_likelihood, log_prior, int(seed), bool(use_graph)
+        self.a, self.de_fraction, self.g0, self.sigma = float(a), float(de_fraction), g0, float(sigma)
+        dev = self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        E, K, d = self.E, self.K, self.d
+        H = self.H = K // 2
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=dev)                # noqa: E731
+        self._beta = torch.as_tensor(self.betas, device=dev).clone()
+        self.theta = torch.as_tensor(np.ascontiguousarray(t0.reshape(E, K, d)), device=dev).clone()
+        self.prop, self.prop_loglik, self.prop_logprior, self.log_q = z(E, H, d), z(E, H), z(E, H), z(E, H)
+        self.state, self.accepted = z(R, dt=torch.int64), z(E, K, dt=torch.int64)
+        self.swap_attempts, self.swap_accepted = z(R, T - 1, dt=torch.int64), z(R, T - 1, dt=torch.int64)
+        self.steps = 0
+        self.trace = self.loglik_trace = self.logprior_trace = None                          # of the last kept run
+        self._traces = (None, None, None)
+        self._window = (0, 0, 1)                                                             # trace_first, trace_len, thin
+        self._graph, self._graph_key = None, None
+        halves = ([], [])
+        for h in (0, 1):                                                                     # the starts, half by half
+            self.prop.copy_(self.theta[:, h * H:(h + 1) * H])
+            for f, got in zip((self.f_lik, self.f_prior), halves):
+                got.append(f(self.prop.view(E * H, d)).reshape(E, H).clone())
+        self.loglik, self.logprior = (torch.cat(got, dim=1).contiguous() for got in halves)
+        finite = torch.isfinite(self.loglik) & torch.isfinite(self.logprior)
+        if not bool(finite.all()):
+            raise ValueError(f'{int((~finite).sum())} of the {E * K} starts have a log likelihood or a log prior that is not '
+                             'finite: every walker must start inside the support')
+        self._launch()                                                                       # launch 0: the proposals of half-step 1
+
+    @staticmethod
+    def check_ladder(betas):
+        """the ladder as a float64 array, or ValueError: T >= 1, finite, strictly decreasing from 1, >= 0"""
+        b = np.array(betas, dtype=np.float64).reshape(-1)
+        if b.size < 1 or not np.isfinite(b).all():
+            raise ValueError(f'the ladder needs T >= 1 finite inverse temperatures (got {betas})')
+        if b[0] != 1.0 or np.any(np.diff(b) >= 0.0) or b[-1] < 0.0:
+            raise ValueError(f'the ladder must decrease strictly from 1 and stay >= 0 (got {b.tolist()})')
+        return b
+
+    @staticmethod
+    def ladder(n_temperatures: int = 8, beta_min: float = 1e-2, include_prior: bool = False):
+        """n_temperatures inverse temperatures beta_min^(t / (n - 1)), from 1 down to beta_min, and a final 0 when include_prior
+        (T = n_temperatures + 1 then)"""
+        n = int(n_temperatures)
+        if n < 1 or (n > 1 and not 0.0 < beta_min < 1.0):
+            raise ValueError('the ladder needs n_temperatures >= 1 and 0 < beta_min < 1')
+        b = np.ones(1) if n == 1 else float(beta_min) ** (np.arange(n) / (n - 1.0))
+        b[0] = 1.0
+        return DeviceTemperedEnsemble.check_ladder(np.append(b, 0.0) if include_prior else b)
+
+    @staticmethod
+    def ball(center, scale, n_walkers: int, n_temperatures: int = 1, n_replicas: int = 1, seed: int = 0):
+        """(n_replicas, n_temperatures, n_walkers, d) starts center + scale * N(0, 1) from np.random.default_rng(seed), as
+        `DeviceEnsemble.ball`"""
+        center = np.atleast_1d(np.asarray(center, dtype=np.float64))
+        rng = np.random.default_rng(seed)
+        return center + np.asarray(scale, dtype=np.float64) * rng.standard_normal((int(n_replicas), int(n_temperatures),
+                                                                                   int(n_walkers), center.size))
+
+    def _launch(self):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                    # noqa: E731
+        first, length, thin = self._window
+        swaps = (p(self.swap_attempts), p(self.swap_accepted)) if self.T > 1 else (None, None)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_tempered_ensemble_step_f64_dev(
+                self.R, self.T, self.K, self.d, self.seed, self.a, self.de_fraction, self.g0, self.sigma, p(self._beta), first, length,
+                thin, p(self.theta), p(self.loglik), p(self.logprior), p(self.prop), p(self.prop_loglik), p(self.prop_logprior),
+                p(self.log_q), p(self.state), p(self.accepted), *swaps, *[p(t) for t in self._traces], None,
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _step(self):
+        for _ in range(2):
+            flat = self.prop.view(self.E * self.H, self.d)
+            self.prop_loglik.view(-1).copy_(self.f_lik(flat))
+            self.prop_logprior.view(-1).copy_(self.f_prior(flat))
+            self._launch()
+
+    def _prepare(self):
+        """the graph is (re)recorded when a trace buffer or the trace window moves: a recorded launch carries them by value.
+        The steps that recording runs are undone."""
+        key = tuple(t.data_ptr() if t is not None else 0 for t in self._traces) + self._window
+        if not self.use_graph or (self._graph is not None and self._graph_key == key):
+            return
+        kept = (self.theta, self.loglik, self.logprior, self.prop, self.prop_loglik, self.prop_logprior, self.log_q, self.state,
+                self.accepted, self.swap_attempts, self.swap_accepted)
+        saved = [t.clone() for t in kept]
+        self._graph = None                                                                   # (frees the old recording first)
+        self._graph, _ = capture_graph(self._step, self.device)
+        self._graph_key = key
+        for t, s in zip(kept, saved):
+            t.copy_(s)
+
+    def run(self, n_steps: int, keep: bool = True, thin: int = 1):
+        """Advance every ensemble n_steps whole steps (two half-steps and the swaps that are due).  Returns the
+        (ceil(n_steps / thin), R, T, K, d) trace as a device tensor if `keep` -- steps 1, 1 + thin, ... of this call, each as the
+        swaps left it -- and keeps it with its (rows, R, T, K) log likelihoods and log priors as `trace`, `loglik_trace`,
+        `logprior_trace` for `cold`, `mean_loglik` and `log_evidence`."""
+        import torch
+        n_steps, thin = int(n_steps), int(thin)
+        if n_steps < 0 or thin < 1:
+            raise ValueError('n_steps >= 0 and thin >= 1')
+        rows = -(-n_steps // thin)
+        E, K, d = self.E, self.K, self.d
+        new = lambda *s: torch.empty(s, dtype=torch.float64, device=self.device)              # noqa: E731
+        self._traces = (new(rows, E, K, d), new(rows, E, K), new(rows, E, K)) if keep and rows else (None, None, None)
+        self._window = (self.steps, rows, thin) if self._traces[0] is not None else (0, 0, 1)
+        if n_steps:
+            self._prepare()
+        for _ in range(n_steps):
+            if self.use_graph:
+                self._graph.replay()
+            else:
+                self._step()
+        self.steps += n_steps
+        traces = self._traces if self._traces[0] is not None or not keep else (new(0, E, K, d), new(0, E, K), new(0, E, K))
+        self._traces = (None, None, None)
+        self._window = (0, 0, 1)
+        if not keep:
+            self.trace = self.loglik_trace = self.logprior_trace = None
+            return None
+        shape = (traces[0].shape[0], self.R, self.T, K)
+        self.trace, self.loglik_trace, self.logprior_trace = traces[0].view(*shape, d), traces[1].view(shape), traces[2].view(shape)
+        return self.trace
+
+    def _kept(self):
+        if self.trace is None:
+            raise ValueError('no trace: the last run was not kept')
+        return self.trace
+
+    def cold(self, means: bool = False):
+        """the t = 0 slice of the last kept trace, (rows, R, K, d): the posterior's draws, which `marginals` pools as
+        cold().reshape(rows, R * K, d); with `means` the R ensemble-mean series (rows, R, d) that `diagnostics.summary` reads
+        (the walkers of one ensemble are not independent chains)"""
+        cold = self._kept()[:, :, 0]
+        return cold.mean(dim=2) if means else cold
+
+    def swap_rates(self):
+        """(R, T - 1): the fraction of the walker pairs of (t, t + 1) offered a swap that took it"""
+        return self.swap_accepted.double() / self.swap_attempts.double().clamp(min=1.0)
+
+    def move_rates(self):
+        """(R, T): the fraction of its move proposals an ensemble's walkers accepted"""
+        return self.accepted.double().mean(dim=1).view(self.R, self.T) / max(1, self.steps)
+
+    def mean_loglik(self, burn: int = 0):
+        """(R, T): the mean log likelihood at every temperature over the walkers and the rows [burn:] of the last kept run"""
+        self._kept()
+        if not 0 <= int(burn) < self.loglik_trace.shape[0]:
+            raise ValueError(f'burn must leave a row of the {self.loglik_trace.shape[0]} kept')
+        return self.loglik_trace[int(burn):].mean(dim=(0, 3))
+
+    @staticmethod
+    def evidence_from(mean_loglik, betas):
+        """Thermodynamic integration, log Z = integral over [0, 1] of E_beta[l] d beta, by the trapezoid rule on the ladder.
+        mean_loglik: (R, T).  Returns dict(log_z (R,) per replica, discretisation (R,): |log_z - the trapezoid over every second
+        ladder point (both ends kept)|, NaN for T < 3; mean: of log_z; spread: its standard deviation over the replicas, NaN for
+        R = 1).  ValueError when the ladder does not end at 0: the integral needs the prior's end."""
+        b = DeviceTemperedEnsemble.check_ladder(betas)
+        if b[-1] != 0.0:
+            raise ValueError(f'log_evidence needs a ladder that ends at beta = 0 (include_prior=True); this one ends at {b[-1]}')
+        ml = np.asarray(mean_loglik, dtype=np.float64).reshape(-1, b.size)
+        trap = lambda idx: (0.5 * (ml[:, idx[:-1]] + ml[:, idx[1:]]) * (b[idx[:-1]] - b[idx[1:]])).sum(axis=1)   # noqa: E731
+        fine = np.arange(b.size)
+        coarse = np.union1d(fine[::2], fine[-1:])
+        log_z = trap(fine)
+        disc = np.abs(log_z - trap(coarse)) if b.size >= 3 else np.full_like(log_z, np.nan)
+        return dict(log_z=log_z, discretisation=disc, mean=float(log_z.mean()),
+                    spread=float(log_z.std(ddof=1)) if log_z.size > 1 else float('nan'))
+
+    def log_evidence(self, burn: int = 0):
+        """`evidence_from(mean_loglik(burn), betas)`: the log evidence per replica, its discretisation estimate and its spread
+        over the replicas"""
+        ml = self.mean_loglik(burn).cpu().numpy() if self.betas[-1] == 0.0 else np.zeros((self.R, self.T))   # (no ladder end: raises)
+        return self.evidence_from(ml, self.betas)

@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "pem_common.h"
+#include "pem_ensemble_moves.h"
 #include "pem_hip.h"
 #include "pem_philox.h"
 
@@ -38,22 +39,13 @@ namespace {
 
 constexpr int THREADS = 256;
 constexpr int MAX_HALF = PEM_ENSEMBLE_MAX_WALKERS / 2;
-constexpr int DRAW_COLS = 6;   // move, z or g, j1, j2, u_acc, u_move
-
-constexpr uint32_t PURPOSE_MOVE = 0x454E0000u;
-constexpr uint32_t PURPOSE_PROPOSE = 0x454E0001u;
-constexpr uint32_t PURPOSE_ACCEPT = 0x454E0002u;
 
 using pem::Philox4;
 using pem::philox4x32_10;
 using pem::u53;
-
-// a standard normal from (2k + 1) 2^-53 for a 52-bit k: strictly inside (0, 1), never +-inf.  Out of line, a leaf: with the
-// library normcdfinv body inlined into the propose loop the kernel is allocated 418 vector registers instead of 56.
-__device__ __attribute__((noinline)) double normal_of(uint32_t hi, uint32_t lo) {
-    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-    return normcdfinv((double)(2 * k + 1) * 0x1.0p-53);
-}
+using pem::ens::DRAW_COLS;
+using pem::ens::PURPOSE_ACCEPT;
+using pem::ens::PURPOSE_MOVE;
 
 __global__ __launch_bounds__(THREADS) void ensemble_step_kernel(int K, int d, uint32_t k0, uint32_t k1, double a, double de_fraction,
                                                                 double g0, double sigma, uint64_t trace_first, uint64_t trace_len,
@@ -115,24 +107,13 @@ __global__ __launch_bounds__(THREADS) void ensemble_step_kernel(int K, int d, ui
     const double u_move = u53(mv.x, mv.y);
     const bool de = u_move < de_fraction;
     for (int m = tid; m < H; m += THREADS) {
-        const Philox4 r = philox4x32_10((uint32_t)e, (uint32_t)(s + 1), PURPOSE_PROPOSE, (uint32_t)m, k0, k1);
-        const int j1 = (int)(((uint64_t)r.x * (uint64_t)H) >> 32);
-        int j2 = -1;
-        double coef, q;
-        if (de) {
-            j2 = (int)(((uint64_t)r.y * (uint64_t)(H - 1)) >> 32);
-            if (j2 >= j1) j2 += 1;
-            coef = g0 * (1.0 + sigma * normal_of(r.z, r.w));
-            q = 0.0;
-        } else {
-            const double t = (a - 1.0) * u53(r.z, r.w) + 1.0;
-            coef = t * t / a;
-            q = (double)(d - 1) * log(coef);
-        }
+        const pem::ens::Move w = pem::ens::draw_move((uint32_t)e, (uint32_t)(s + 1), (uint32_t)m, H, d, de, a, g0, sigma, k0, k1);
+        const int j1 = w.j1, j2 = w.j2;
+        const double coef = w.coef;
         s_coef[m] = coef;
         s_j1[m] = j1;
         s_j2[m] = j2;
-        lq[m] = q;
+        lq[m] = w.log_q;
         if (dr) {
             double* row = dr + (size_t)m * DRAW_COLS;
             row[0] = de ? 1.0 : 0.0;
@@ -151,9 +132,9 @@ __global__ __launch_bounds__(THREADS) void ensemble_step_kernel(int K, int d, ui
         double y;
         if (de) {
             const double x2 = th[(size_t)(cb + s_j2[m]) * dd + j];
-            y = xw + c * (x1 - x2);
+            y = pem::ens::de_point(c, xw, x1, x2);
         } else {
-            y = x1 + c * (xw - x1);
+            y = pem::ens::stretch_point(c, xw, x1);
         }
         pr[idx] = y;
     }

@@ -990,6 +990,53 @@ int pem_ensemble_step_f64_dev(size_t n_ensembles, int n_walkers, int ndim, uint6
                               double* prop, const double* prop_logp, double* log_q, uint64_t* state, uint64_t* accepted,
                               double* trace, double* logp_trace, double* draws, pem_stream_t stream);
 
+/* ---- replica exchange over the ensemble sampler, one launch per half-step (csrc/pem_tempering.hip,
+ * calibration.DeviceTemperedEnsemble) -- parallel tempering as ptemcee runs it over emcee (third-party and absent: parity UNPINNED;
+ * the rules are the ones below, restated in tests/tempering_np.py).  n_replicas = R independent replicas of a ladder of
+ * n_temperatures = T inverse temperatures 1 = beta[0] > beta[1] > ... > beta[T-1] >= 0; ensemble e = r T + t samples
+ * prior(x) likelihood(x)^beta[t] with K walkers in the two fixed halves of pem_ensemble_step_f64_dev, E = R T ensembles in all,
+ * one workgroup per REPLICA.  All state is in DEVICE arrays of the caller, beta included:
+ *   beta [T]                      the ladder; the caller guarantees finite, strictly decreasing values in [0, 1]
+ *   theta [E][K][d]               the walkers;  loglik [E][K], logprior [E][K]: their log likelihoods and log priors, all finite
+ *   prop [E][H][d]                the pending proposals: the caller evaluates both functions on prop seen as (E H, d) and writes
+ *   prop_loglik, prop_logprior [E][H]   the values here between two launches
+ *   log_q [E][H]                  log of the proposal weight of each pending proposal
+ *   state [R]                     launches seen by the replica (the caller zeroes it; a captured graph advances it)
+ *   accepted [E][K]               accepted moves per walker
+ *   swap_attempts, swap_accepted [R][T-1]   walker pairs offered a swap / swapped, per (replica, lower temperature t of the pair
+ *                                 (t, t + 1)); may be NULL when T == 1
+ *   trace [trace_len][E][K][d], loglik_trace, logprior_trace [trace_len][E][K]   each may be NULL
+ *   draws NULL or [E][H][6]       as pem_ensemble_step_f64_dev reports them
+ * Launch s = state[r].  s == 0: nothing is pending.  s >= 1 resolves half-step s with pem_ensemble_step_f64_dev's draws (the
+ * ensemble word of the counter is e): walker m of the moving half takes its proposal, prop_loglik and prop_logprior iff both
+ * values are finite and
+ *   log(u_acc) < (log_q + (prop_logprior - logprior)) + beta[t] (prop_loglik - loglik)
+ * at every temperature, beta = 0 included, so that beta loglik is never 0 inf.  When s is even, step n = s / 2 has ended and the
+ * SWAPS of step n follow: in every replica the pairs (t, t + 1) with t = n mod 2, n mod 2 + 2, ... and t + 1 < T (every ensemble
+ * is in at most one pair; the top of the ladder idles when its pair is not due); walker k of t and walker k of t + 1 exchange
+ * theta, loglik and logprior iff
+ *   log(u_swap) < (beta[t] - beta[t+1]) (loglik[t+1][k] - loglik[t][k])
+ * with u_swap = u53(x, y) of Philox4x32-10(counter = (r T + t, n mod 2^32, 0x454E0003, k), key = seed) -- the purpose word keeps
+ * it apart from the move draws 0x454E0000 ... 0x454E0002 -- and the pair's counters advance by K and by the number swapped.  Then,
+ * with q = n - 1 - trace_first, the ladder as the swaps left it goes to row q / thin of the traces when q >= 0, q mod thin == 0
+ * and q / thin < trace_len.  Every launch then proposes half-step s + 1 as pem_ensemble_step_f64_dev does and sets
+ * state[r] = s + 1.  Products and sums are rounded separately, and log_q = (d - 1) log z of the stretch takes its log through
+ * IEEE operations alone (csrc/pem_ensemble_moves.h, log_restatable: fdlibm's e_log.c, below 1 ulp), so that the restatement holds
+ * EVERY state word bit for bit; pem_ensemble_step_f64_dev asks the library, whose last bit is its own.  With T == 1 and
+ * logprior == 0 the launch therefore visits pem_ensemble_step_f64_dev's points on finite values -- the same draws, proposals and
+ * decisions, log_q within an ulp.  No atomics, no communication between workgroups, no cooperative launch: the same bits on
+ * every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: n_replicas 0, n_temperatures < 1, n_replicas n_temperatures
+ * or n_temperatures n_walkers ndim above INT_MAX, everything pem_ensemble_step_f64_dev refuses about n_walkers, ndim, a,
+ * de_fraction, g0, sigma and thin, a NULL required array, NULL swap counters with T > 1, a trace with trace_len 0.           */
+int pem_tempered_ensemble_step_f64_dev(size_t n_replicas, int n_temperatures, int n_walkers, int ndim, uint64_t seed, double a,
+                                       double de_fraction, double g0, double sigma, const double* beta, uint64_t trace_first,
+                                       size_t trace_len, uint64_t thin, double* theta, double* loglik, double* logprior,
+                                       double* prop, const double* prop_loglik, const double* prop_logprior, double* log_q,
+                                       uint64_t* state, uint64_t* accepted, uint64_t* swap_attempts, uint64_t* swap_accepted,
+                                       double* trace, double* loglik_trace, double* logprior_trace, double* draws,
+                                       pem_stream_t stream);
+
 /* ---- MCMC chain diagnostics (hallthrusterpem_amd/diagnostics.py; the lag sums of uq.autocorrelation at
  * scripts/pem_v0/mcmc.py:310 -- uqtils, third-party, parity UNPINNED).  x: fp64 [n_rows][ld], unit column stride (a
  * (n, K, d) trace seen as n rows of K*d series; the pointer needs only 8-byte alignment).  Segment s is rows
