@@ -27,7 +27,8 @@ POWELL_MAX_DIM, POWELL_STATE_WORDS = 32, 24   # PEM_POWELL_MAX_DIM / PEM_POWELL_
 POWELL_SCALARS, POWELL_VEC_ROWS = 20, 6       # PEM_POWELL_SCALARS / PEM_POWELL_VEC_ROWS: its doubles and d-vectors per search
 DRAM_MAX_DIM = 32              # PEM_DRAM_MAX_DIM: dimensions of pem_dram_step_f64_dev (one lane per dimension)
 ENSEMBLE_MAX_DIM, ENSEMBLE_MAX_WALKERS = 32, 1024   # PEM_ENSEMBLE_MAX_DIM / _MAX_WALKERS: dimensions and walkers per ensemble of pem_ensemble_step_f64_dev
-CHAIN_TIME_BLOCK = 4096             # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
+SMC_MAX_DIM, SMC_MAX_PARTICLES, SMC_BISECTIONS = 32, 16384, 52   # PEM_SMC_*: dimensions, particles per population and ESS halvings of pem_smc_stage_f64_dev
+CHAIN_TIME_BLOCK = 4096           # PEM_CHAIN_TIME_BLOCK: rows per workspace partial of pem_chain_autocov_f64_dev
 MARGINALS_MAX_PAR, MARGINALS_MAX_BINS = 32, 64   # PEM_MARGINALS_MAX_PAR / _MAX_BINS: parameters and bins of pem_chain_hist_f64_dev
 HIST_ROW_TILE = 128                 # PEM_HIST_ROW_TILE: rows it bins per stage
 KDE_MAX_GRID, KDE_ROW_BLOCK = 4096, 4096   # PEM_KDE_MAX_GRID / PEM_KDE_ROW_BLOCK: grid points and rows per workspace partial of pem_chain_kde_f64_dev
@@ -146,6 +147,9 @@ SIGNATURES = {
                                             + [_dp] * 10 + [_dp]),
     'pem_tempered_ensemble_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, _dp, C.c_uint64, _sz,
                                                      C.c_uint64] + [_dp] * 15 + [_dp]),
+    'pem_smc_stage_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, C.c_uint32] + [_dp] * 17 + [_sz, _dp, _dp]),
+    'pem_smc_move_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, C.c_uint32, C.c_uint32, C.c_int] + [_dp] * 12
+                                       + [_dp]),
     'pem_sample_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _sz, _dp]),
     'pem_sample_tiled_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_sample_lhs_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),

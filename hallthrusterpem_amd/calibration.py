@@ -34,6 +34,9 @@ ensemble's walkers per evaluation, one launch of `pem_ensemble_step_f64_dev` per
 `DeviceTemperedEnsemble` is replica exchange over it for a posterior with more than one mode: a ladder of tempered ensembles per
 replica, swaps between neighbouring temperatures inside `pem_tempered_ensemble_step_f64_dev`, the log evidence by thermodynamic
 integration.
+`DeviceSMC` is tempered sequential Monte Carlo (TMCMC) for when there is no start at all: populations of particles drawn from the
+prior, the next temperature found from the particles, resampling and Metropolis moves in `pem_smc_stage_f64_dev` /
+`pem_smc_move_f64_dev`, equally weighted posterior draws and the log evidence in one pass.
 """
 import ctypes as C
 import math
@@ -1094,3 +1097,202 @@ class DeviceTemperedEnsemble:
         over the replicas"""
         ml = self.mean_loglik(burn).cpu().numpy() if self.betas[-1] == 0.0 else np.zeros((self.R, self.T))   # (no ladder end: raises)
         return self.evidence_from(ml, self.betas)
+
+
+class SMCResult:
+    """What `DeviceSMC.run` returns.  theta (R, N, d), loglik, logprior (R, N): device tensors, N equally weighted draws of the
+    posterior per population.  log_evidence (R,), stages (R,), converged (R,) (beta reached 1), flags (R,) (bit 0: a Cholesky
+    factor was refused and the previous one kept; bit 1: no particle had a finite log likelihood): host arrays.  betas, ess,
+    acceptance, log_evidence_increments: (R, stages) host arrays, one column per stage, NaN past a population's last stage."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def as_trace(self):
+        """The particles as an (N, R, d) trace: N rows of R 'chains', what `marginals.corner(trace, names, burnin=0)` and
+        `predictive.flatten_chain` read.  The rows are equally weighted draws, not successive states of a chain: `diagnostics`
+        (split R-hat, autocorrelation, chain ESS) DOES NOT APPLY to them; `ess` per stage is the particle diagnostic."""
+        return self.theta.permute(1, 0, 2).contiguous()
+
+
+class DeviceSMC:
+    """Tempered sequential Monte Carlo (TMCMC, Ching & Chen 2007; the SMC sampler of Del Moral et al. 2006; PyMC's sample_smc --
+    all third-party and absent here: parity UNPINNED; the rules are this project's own, include/pem_hip.h and DESIGN.md 4.6.9, and
+    tests/smc_np.py restates them) with the whole sampler on the device: R independent populations of N particles are carried
+    from the prior to the posterior along prior x likelihood^beta.  It needs NO start, NO proposal covariance and NO ladder: the
+    next beta is the one that brings the effective sample size of the incremental weights down to tau N (bisection inside
+    `pem_smc_stage_f64_dev`), the proposal is the weighted covariance of the particles, and the result is N equally weighted
+    posterior draws per population AND the log evidence.
+
+    One stage is [stage launch ; (log_likelihood(prop), log_prior(prop) ; move launch) x n_mcmc] on one stream: the stage launch
+    (one workgroup per population) finds beta', adds log mean w to the evidence, factorises scale^2 cov + eps I, resamples
+    systematically and proposes; each move launch (`pem_smc_move_f64_dev`, all R N particles) resolves a random-walk Metropolis
+    proposal against prior x likelihood^beta' and proposes the next, the last one with propose = 0.  With `use_graph` a stage is
+    one hipGraph replay without parallel branches.  A finished population ignores further replays.
+
+    log_likelihood, log_prior: callables on an (R N, d) float64 device tensor returning (R N,) values THAT DO NOT DEPEND ON THE
+    ROW: closed forms, or `.log_likelihood` and `.log_prior` of a `SystemPosterior` / `JionPosterior` / `SurrogatePosterior` built
+    with n_chains=R*N, shared_nuisance=True, fresh_nuisance=False.
+
+    theta0: (N, d) or (R, N, d) draws FROM THE PRIOR (`prior_draws` makes them).  THE EVIDENCE IS THE MEAN OF THE LIKELIHOOD UNDER
+    THE LAW theta0 WAS DRAWN FROM: starts from anything else give the evidence against that law, and posterior draws only if
+    log_prior is that law's density.  Every start needs a finite log prior; a log likelihood that is not finite is allowed and
+    has weight 0; a population without any finite log likelihood is refused.  scale: None = 2.38 / sqrt(d).  There is no CPU
+    path."""
+
+    def __init__(self, log_likelihood, log_prior, theta0, n_populations: int = 1, tau: float = 0.5, n_mcmc: int = 3,
+                 scale: float | None = None, eps: float = 1e-12, seed: int = 0, device=None, use_graph: bool = True):
+        import torch
+        if isinstance(theta0, torch.Tensor):
+            if device is None:
+                device = theta0.device
+            theta0 = theta0.detach().cpu().numpy()
+        t0 = np.asarray(theta0, dtype=np.float64)
+        if t0.ndim == 2 and int(n_populations) == 1:
+            t0 = t0[None]
+        if t0.ndim != 3 or int(n_populations) not in (1, t0.shape[0]):
+            raise ValueError('theta0 must be (N, d) with n_populations == 1, or (R, N, d)')
+        self.R, self.N, self.d = t0.shape
+        if not 1 <= self.d <= _lib.SMC_MAX_DIM:
+            raise ValueError(f'DeviceSMC samples 1 to {_lib.SMC_MAX_DIM} parameters (got {self.d})')
+        if self.R < 1 or not 2 <= self.N <= _lib.SMC_MAX_PARTICLES:
+            raise ValueError(f'DeviceSMC needs 2 <= N <= {_lib.SMC_MAX_PARTICLES} particles per population (got {self.N})')
+        if not np.isfinite(t0).all():
+            raise ValueError(f'{int((~np.isfinite(t0).all(axis=-1)).sum())} of the {self.R * self.N} starts have a coordinate that is '
+                             'not finite')
+        if not 0.0 < tau < 1.0:
+            raise ValueError(f'tau must be in (0, 1) (got {tau})')
+        if int(n_mcmc) != n_mcmc or int(n_mcmc) < 1:
+            raise ValueError(f'n_mcmc must be a whole number >= 1 (got {n_mcmc})')
+        scale = 2.38 / math.sqrt(self.d) if scale is None else float(scale)
+        if not (scale > 0.0 and math.isfinite(scale) and eps >= 0.0):
+            raise ValueError('need a finite scale > 0 and eps >= 0')
+        if device is not None and torch.device(device).type != 'cuda':
+            raise ValueError(f"DeviceSMC runs on the GPU only (got device '{device}')")
+        self.f_lik, self.f_prior, self.seed, self.use_graph = log_likelihood, log_prior, int(seed), bool(use_graph)
+        self.tau, self.n_mcmc, self.scale, self.eps = float(tau), int(n_mcmc), scale, float(eps)
+        dev = self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        R, N, d = self.R, self.N, self.d
+        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=dev)                # noqa: E731
+        self.theta = torch.as_tensor(np.ascontiguousarray(t0), device=dev).clone()
+        flat = self.theta.view(R * N, d)
+        self.loglik = self.f_lik(flat).reshape(R, N).clone()
+        self.logprior = self.f_prior(flat).reshape(R, N).clone()
+        if not bool(torch.isfinite(self.logprior).all()):
+            raise ValueError(f'{int((~torch.isfinite(self.logprior)).sum())} of the {R * N} starts have a log prior that is not '
+                             'finite: the starts are draws from the prior')
+        if not bool(torch.isfinite(self.loglik).any(dim=1).all()):
+            raise ValueError('a population has no start with a finite log likelihood')
+        self.beta, self.log_evidence, self.stage = z(R), z(R), z(R, dt=torch.int64)
+        self.L, self.prop, self.prop_loglik, self.prop_logprior = z(R, d, d), z(R, N, d), z(R, N), z(R, N)
+        self.accept_count, self.accepted = z(R, N, dt=torch.int32), z(R, dt=torch.int64)
+        self.flags, self.moves_active = z(R, dt=torch.int32), z(R, dt=torch.int32)
+        self.scratch = z(R, N, d + 2)
+        self._hist = None                                                                    # (4, R, history_len), made by run
+        self._graph = None
+
+    @staticmethod
+    def prior_draws(names, priors=None, n_particles: int = 1024, n_populations: int = 1, seed: int = 0, method: str = 'sobol',
+                    device=None):
+        """(n_populations, n_particles, len(names)) draws of `names` from their priors (None: PEM_V0_PRIORS) as a device tensor,
+        through `sampling.Design`: population r is points 0 ... n_particles - 1 of the design with (seed, stream = r) -- for
+        'sobol' a Sobol' set with its own random digital shift per population, for 'mc' independent draws."""
+        import torch
+        if method not in ('sobol', 'mc'):
+            raise ValueError(f"method must be 'sobol' or 'mc' (got '{method}')")
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty((int(n_populations), len(names), int(n_particles)), dtype=torch.float64, device=dev)
+        for r in range(int(n_populations)):
+            Design(priors=priors, names=names, seed=seed, stream=r).fill(out[r], method=method)
+        return out.transpose(1, 2).contiguous()
+
+    def _args(self):
+        return (self.R, self.N, self.d, self.seed, self.tau, self.scale, self.eps, self.n_mcmc)
+
+    def _launch_stage(self, record=None):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                    # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_smc_stage_f64_dev(
+                *self._args(), p(self.theta), p(self.loglik), p(self.logprior), p(self.beta), p(self.log_evidence), p(self.stage),
+                p(self.L), p(self.prop), p(self.accept_count), p(self.accepted), p(self.flags), p(self.moves_active), p(self.scratch),
+                *[p(h) for h in self._hist], self._hist.shape[2], p(record),
+                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _launch_move(self, move: int, propose: bool, record=None):
+        import torch
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                    # noqa: E731
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_smc_move_f64_dev(
+                *self._args(), int(move), 1 if propose else 0, p(self.theta), p(self.loglik), p(self.logprior), p(self.beta),
+                p(self.stage), p(self.L), p(self.prop), p(self.prop_loglik), p(self.prop_logprior), p(self.accept_count),
+                p(self.moves_active), p(record), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def _stage(self):
+        self._launch_stage()
+        flat = self.prop.view(self.R * self.N, self.d)
+        for m in range(1, self.n_mcmc + 1):
+            self.prop_loglik.view(-1).copy_(self.f_lik(flat))
+            self.prop_logprior.view(-1).copy_(self.f_prior(flat))
+            self._launch_move(m, m < self.n_mcmc)
+
+    def _state(self):
+        return (self.theta, self.loglik, self.logprior, self.beta, self.log_evidence, self.stage, self.L, self.prop, self.prop_loglik,
+                self.prop_logprior, self.accept_count, self.accepted, self.flags, self.moves_active, self.scratch, self._hist)
+
+    def _prepare(self, history_len: int):
+        """the history arrays grow to hold every stage of this run; a recorded launch carries them by value, so the graph is
+        recorded again when they move.  The stages that recording runs are undone."""
+        import torch
+        if self._hist is None or self._hist.shape[2] < history_len:
+            hist = torch.zeros((4, self.R, history_len), dtype=torch.float64, device=self.device)
+            if self._hist is not None:
+                hist[:, :, :self._hist.shape[2]] = self._hist
+            self._hist, self._graph = hist, None
+        if not self.use_graph or self._graph is not None:
+            return
+        saved = [t.clone() for t in self._state()]
+        self._graph, _ = capture_graph(self._stage, self.device)
+        for t, s in zip(self._state(), saved):
+            t.copy_(s)
+
+    def run(self, max_stages: int = 200, check_every: int = 4):
+        """Replay stages, reading beta and flags back once per `check_every` stages, until every population is at beta = 1, or
+        flag bit 1 is up, or max_stages stages of this call have run.  The result does not depend on check_every: a finished
+        population ignores the replays past its end.  Returns an `SMCResult`; a later call continues."""
+        import torch
+        max_stages, check_every = int(max_stages), int(check_every)
+        if max_stages < 0 or check_every < 1:
+            raise ValueError('max_stages >= 0 and check_every >= 1')
+        done = int(self.stage.max())
+        self._prepare(done + max(max_stages, 1))
+        ran = 0
+        while ran < max_stages:
+            beta, flags = self.beta.cpu().numpy(), self.flags.cpu().numpy()
+            if (beta == 1.0).all() or (flags & 2).any():
+                break
+            for _ in range(min(check_every, max_stages - ran)):
+                if self.use_graph:
+                    self._graph.replay()
+                else:
+                    self._stage()
+                ran += 1
+        return self.result()
+
+    def result(self):
+        """the `SMCResult` of the state as it stands"""
+        stages = self.stage.cpu().numpy().astype(np.int64)
+        hist = self._hist.cpu().numpy().copy() if self._hist is not None else np.zeros((4, self.R, 0))
+        n = int(stages.max()) if stages.size else 0
+        hist = hist[:, :, :n]
+        # the acceptance of a stage is closed by the stage launch that follows it; where none has followed, from the same counts
+        count = self.accept_count.cpu().numpy().astype(np.int64).sum(axis=1)
+        active = self.moves_active.cpu().numpy().astype(bool)
+        for r in np.nonzero(active & (stages >= 1) & (stages <= hist.shape[2]))[0]:
+            hist[2, r, stages[r] - 1] = float(count[r]) / (float(self.N) * float(self.n_mcmc))
+        hist[:, np.arange(n)[None, :] >= stages[:, None]] = np.nan
+        beta = self.beta.cpu().numpy()
+        return SMCResult(theta=self.theta.clone(), loglik=self.loglik.clone(), logprior=self.logprior.clone(),
+                         log_evidence=self.log_evidence.cpu().numpy(), betas=hist[0], ess=hist[1], acceptance=hist[2],
+                         log_evidence_increments=hist[3], stages=stages, converged=beta == 1.0,
+                         flags=self.flags.cpu().numpy().astype(np.uint32))

@@ -1037,6 +1037,83 @@ int pem_tempered_ensemble_step_f64_dev(size_t n_replicas, int n_temperatures, in
                                        double* trace, double* loglik_trace, double* logprior_trace, double* draws,
                                        pem_stream_t stream);
 
+/* ---- tempered sequential Monte Carlo, two launches (csrc/pem_smc.hip, calibration.DeviceSMC) -------------------------------
+ * TMCMC (Ching & Chen 2007) / the SMC sampler of Del Moral et al. 2006 as PyMC's sample_smc runs it (third-party and absent:
+ * parity UNPINNED; the rules are the ones below, restated in tests/smc_np.py).  n_populations = R independent populations of
+ * n_particles = N particles of dimension ndim = d move from the law the caller drew them from (beta = 0) to prior x likelihood
+ * (beta = 1) along prior x likelihood^beta.  All state is in DEVICE arrays of the caller:
+ *   theta [R][N][d], loglik [R][N], logprior [R][N]   the particles and their values; logprior finite, loglik may be anything
+ *   beta [R], log_evidence [R]    the inverse temperature reached and the log evidence accumulated (the caller zeroes both)
+ *   stage [R]                     stages completed (the caller zeroes it)
+ *   L [R][d][d]                   lower Cholesky factor of the proposal covariance, row-major
+ *   prop [R][N][d]                the pending proposals: the caller evaluates both functions on prop seen as (R N, d) and writes
+ *   prop_loglik, prop_logprior [R][N]   the values here between two launches
+ *   accept_count [R][N]           uint32: moves of the current stage each particle accepted (what keeps the move launch free of
+ *                                 atomics; the stage launch sums and zeroes it)
+ *   accepted [R]                  accepted moves of the last stage whose moves have ended: set by the stage launch that follows
+ *                                 them and kept until the next stage's moves have ended (the caller zeroes it)
+ *   flags [R]                     bit 0: a Cholesky factor was refused; bit 1: no particle had a finite log likelihood
+ *   moves_active [R]              uint32: set by the stage launch, read by the move launch
+ *   scratch [R][N][d + 2]         the resampling gather's staging area
+ *   hist_beta, hist_ess, hist_accept, hist_dlogz [R][history_len]   per stage s = 0, 1, ... (stages past history_len are not
+ *                                 recorded): beta', ESS(beta'), accepted / (N n_mcmc), the evidence increment
+ *   record (stage launch)  NULL or [R][3N + Nd + 1 + d + d d]: w [N] un-normalised, W [N] normalised, ancestors [N] (as doubles),
+ *                                 the normals of the proposals [N][d], u of the resampler, mean [d], cov [d][d] (before scale, eps)
+ *   record (move launch)   NULL or [R][N][d + 2]: the normals of the proposals it drew [d], then u and the decision (0 / 1) of the
+ *                                 proposal it resolved
+ *
+ * pem_smc_stage_f64_dev: one workgroup of 1024 per population, thread t holding particles t P ... t P + P - 1, P = ceil(N / 1024).
+ *   0. If moves_active: accepted = sum of accept_count, and with s = stage >= 1, hist_accept[s - 1] = accepted / (N n_mcmc).
+ *      If beta is not < 1 the population is finished: moves_active = 0 and nothing else changes, so a replay after that changes
+ *      no word at all.
+ *   1. l_max = the largest finite loglik; a loglik that is not finite has weight 0 at every temperature.  No finite value: bit 1
+ *      of flags is set, moves_active = 0, nothing else changes.  Otherwise w_i(b) = exp((b - beta) (l_i - l_max)) and
+ *      ESS(b) = (sum w)^2 / sum w^2.  beta' = 1 if ESS(1) >= tau N; otherwise PEM_SMC_BISECTIONS halvings of [lo, hi] = [beta, 1],
+ *      mid = 0.5 (lo + hi), lo = mid if ESS(mid) >= tau N else hi = mid, and beta' = lo if lo > beta else hi: every stage advances.
+ *   2. log_evidence += log(sum w(beta') / N) + (beta' - beta) l_max; N counts the particles of weight 0 as well.
+ *   3. mean_j = (sum_i w_i x_ij) / sum w, cov_jk = (sum_i (w_i (x_ij - mean_j)) (x_ik - mean_k)) / sum w, and L = the Cholesky factor
+ *      (column by column, from the lower triangle) of scale^2 cov + eps I, committed only if every pivot is > 0; otherwise L is kept
+ *      whole and bit 0 of flags is set (pem_dram_step_f64_dev's rule).
+ *   4. Systematic resampling: u = u53(x, y) of Philox4x32-10(counter = (population, new stage number mod 2^32, 0x534D0000, 0),
+ *      key = seed); ancestor a_j = the smallest i with C_i > (((j + u) / N) C_{N-1}), clamped to the last particle of positive
+ *      weight.  C is the inclusive cumulative sum of w in this FIXED ORDER: C_i = W_v + (O_t + c_i), where c_i is the running
+ *      sum of thread t's own P weights in particle order, O_t the running sum, from 0, of the totals (last c) of the threads
+ *      before t in its wave of 64 threads, W_v the running sum, from 0, of the totals (O + total of the wave's last thread) of the
+ *      waves before wave v; particles past N count as weight 0.  Every level starts where the one below ends, so C never
+ *      decreases.  theta, loglik and logprior are gathered through scratch; accept_count is zeroed.
+ *   5. The history row s = stage; beta = beta', stage += 1, moves_active = 1.
+ *   6. The proposals of move 1 of the new stage (below).
+ * pem_smc_move_f64_dev: workgroups of 256 over 64 particles each; for the populations with moves_active it resolves proposal
+ * `move` (1 ... n_mcmc) of the stage: a particle takes prop, prop_loglik and prop_logprior iff both values are finite and
+ *   log(u) < (prop_logprior - logprior) + beta (prop_loglik - loglik)
+ * (symmetric proposal; a NaN on either side compares false; refused at beta = 0 as well, so beta loglik is never 0 inf), u =
+ * u53(x, y) of counter (population N + particle, (stage n_mcmc + move) mod 2^32, 0x534D0002, 0), and accept_count += 1.  Unless
+ * propose == 0 it then draws proposal move + 1, y_j = x_j + sum_{i<=j} L_ji z_i (i ascending, products and sums rounded
+ * separately), z_2p and z_2p+1 from counter (population N + particle, (stage n_mcmc + move + 1) mod 2^32, 0x534D0001, p), each
+ * normcdfinv((2k + 1) 2^-53) of a 52-bit k as pem_dram_step_f64_dev draws them.  `stage` is the number of the stage the move
+ * belongs to (1 for the first).  The last move of a stage, move == n_mcmc, must come with propose == 0: its proposals would be
+ * drawn under the word (stage + 1) n_mcmc + 1 of the next stage launch's own.  tau, scale and eps are checked and not used.
+ * No atomics, no communication between workgroups, no cooperative launch: the same bits on every run.
+ * PEM_SMC_MAX_PARTICLES is 16384: what limits it is the one LDS array of N doubles (128 KiB of a CU's 160) in which the stage
+ * workgroup holds l - l_max, then the weights, then their cumulative sums, then the ancestors.
+ * Both refuse with PEM_ERR_INVALID_ARG before the device is looked at: n_populations 0, n_particles outside
+ * [2, PEM_SMC_MAX_PARTICLES], ndim outside [1, PEM_SMC_MAX_DIM], n_populations n_particles above 2^32 - 1, tau not in (0, 1), scale
+ * not finite or not > 0, eps < 0, n_mcmc 0, a NULL required array (everything but record), history_len 0 (stage), move outside
+ * [1, n_mcmc], move == n_mcmc with propose != 0, or n_populations ceil(n_particles / 64) above INT_MAX (move).                                                      */
+#define PEM_SMC_MAX_DIM 32
+#define PEM_SMC_MAX_PARTICLES 16384
+#define PEM_SMC_BISECTIONS 52
+int pem_smc_stage_f64_dev(size_t n_populations, int n_particles, int ndim, uint64_t seed, double tau, double scale, double eps,
+                          uint32_t n_mcmc, double* theta, double* loglik, double* logprior, double* beta, double* log_evidence,
+                          uint64_t* stage, double* L, double* prop, uint32_t* accept_count, uint64_t* accepted, uint32_t* flags,
+                          uint32_t* moves_active, double* scratch, double* hist_beta, double* hist_ess, double* hist_accept,
+                          double* hist_dlogz, size_t history_len, double* record, pem_stream_t stream);
+int pem_smc_move_f64_dev(size_t n_populations, int n_particles, int ndim, uint64_t seed, double tau, double scale, double eps,
+                         uint32_t n_mcmc, uint32_t move, int propose, double* theta, double* loglik, double* logprior,
+                         const double* beta, const uint64_t* stage, const double* L, double* prop, const double* prop_loglik,
+                         const double* prop_logprior, uint32_t* accept_count, const uint32_t* moves_active, double* record,
+                         pem_stream_t stream);
+
 /* ---- MCMC chain diagnostics (hallthrusterpem_amd/diagnostics.py; the lag sums of uq.autocorrelation at
  * scripts/pem_v0/mcmc.py:310 -- uqtils, third-party, parity UNPINNED).  x: fp64 [n_rows][ld], unit column stride (a
  * (n, K, d) trace seen as n rows of K*d series; the pointer needs only 8-byte alignment).  Segment s is rows
