@@ -33,6 +33,8 @@ MARGINALS_MAX_PAR, MARGINALS_MAX_BINS = 32, 64   # PEM_MARGINALS_MAX_PAR / _MAX_
 HIST_ROW_TILE = 128                 # PEM_HIST_ROW_TILE: rows it bins per stage
 KDE_MAX_GRID, KDE_ROW_BLOCK = 4096, 4096   # PEM_KDE_MAX_GRID / PEM_KDE_ROW_BLOCK: grid points and rows per workspace partial of pem_chain_kde_f64_dev
 HEX_MAX_GRID, HEX_ROW_TILE = 64, 128       # PEM_HEX_MAX_GRID / PEM_HEX_ROW_TILE: nx, ny and rows per stage of pem_chain_hex_f64_dev
+INFORMATION_MAX_GROUPS = 32                # PEM_INFORMATION_MAX_GROUPS: column groups of pem_pairwise_lse_f64_dev
+INFORMATION_CHUNK, INFORMATION_INNER_BLOCK = 16, 512   # PEM_INFORMATION_CHUNK / _INNER_BLOCK: columns it stages per step, inner rows per workspace partial
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
 _sz = C.c_size_t
@@ -159,6 +161,8 @@ SIGNATURES = {
     'pem_chain_hist_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, C.c_int, _dp] + [_dp] * 4 + [_dp]),
     'pem_chain_kde_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, _sz, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
     'pem_chain_hex_f64_dev': (C.c_int, [_sz, C.c_int, _sz, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    'pem_pairwise_lse_f64_dev': (C.c_int, [_sz, _sz, C.c_int, _dp, _sz, _dp, _sz, C.c_int, _dp, _dp, _dp, _dp, _sz, _dp]),
+    'pem_pairwise_lse_work_len': (_sz, [_sz, _sz, C.c_int]),
 }
 
 

@@ -1197,6 +1197,37 @@ int pem_chain_kde_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, 
 int pem_chain_hex_f64_dev(size_t n_rows, int n_par, size_t ld, const double* x, int nx, int ny, const double* lattice,
                           uint64_t* counts, pem_stream_t stream);
 
+/* ---- all-pairs Gaussian log-density with a log-sum-exp over the inner draws (csrc/pem_information.hip,
+ * hallthrusterpem_amd/information.py: the nested Monte Carlo estimator of the expected information gain of groups of
+ * measurements, Ryan 2003, Huan & Marzouk 2013; the reference has no such analysis, nothing to pin).
+ *   z_out [n_out][ld_out]  DEVICE, the standardised observations of the outer draws, n_col <= ld_out columns used
+ *   z_in  [n_in][ld_in]    DEVICE, the standardised predictions of the inner draws
+ *   group_end [n_groups]   HOST: group c is the columns group_end[c-1] ... group_end[c] - 1 (group_end[-1] = 0); read and checked
+ *                          before the call returns, it travels as a kernel argument.  Set n_groups is the union of all columns.
+ *   lse, ess [n_out][n_groups + 1]  DEVICE
+ * For every outer row i and set c, all in fp64:
+ *   d2_c(i, j) = sum_{k in c} (z_out[i][k] - z_in[j][k])^2   the direct form, one fma chain in increasing k; the union's d2 is the
+ *                                                            sum of the groups' d2 of the same (i, j), added in group order
+ *   l = -d2 / 2,  m = max_j l,  s1 = sum_j exp(l - m),  s2 = sum_j exp(l - m)^2
+ *   lse[i][c] = m + log s1 - log n_in        ess[i][c] = s1^2 / s2     (1 <= ess <= n_in: the inner draws that carry the sum)
+ * The n_out x n_in matrix is never written: a workgroup owns 32 outer rows and a block of PEM_INFORMATION_INNER_BLOCK inner
+ * rows, stages PEM_INFORMATION_CHUNK columns of both operands at a time, and leaves one (m, s1, s2) per (block, row, set) in
+ * work; a second launch merges the blocks in block order.  No floating-point atomics.  The bits of row i depend on that row,
+ * z_in and the groups only -- not on n_out, the grid or the other rows of the call.
+ * The domain is finite inputs whose d2 stays finite (an infinite d2 for every j of a block gives NaN).
+ * pem_pairwise_lse_work_len: the doubles of work, ceil(n_in / PEM_INFORMATION_INNER_BLOCK) n_out (n_groups + 1) 3; 0 for a
+ * zero size, n_groups outside [1, PEM_INFORMATION_MAX_GROUPS] or a product past size_t.  Host only.
+ * Refused with PEM_ERR_INVALID_ARG before any device call: a zero size, n_groups outside [1, PEM_INFORMATION_MAX_GROUPS], a null
+ * pointer, ld_out or ld_in < n_col, group_end not strictly ascending from above 0 or not ending at n_col, work_len short,
+ * more than 65535 inner blocks, n_col > INT_MAX - PEM_INFORMATION_CHUNK.                                           */
+#define PEM_INFORMATION_MAX_GROUPS 32
+#define PEM_INFORMATION_CHUNK 16
+#define PEM_INFORMATION_INNER_BLOCK 512
+int pem_pairwise_lse_f64_dev(size_t n_out, size_t n_in, int n_col, const double* z_out, size_t ld_out, const double* z_in,
+                             size_t ld_in, int n_groups, const int* group_end, double* lse, double* ess, double* work,
+                             size_t work_len, pem_stream_t stream);
+size_t pem_pairwise_lse_work_len(size_t n_out, size_t n_in, int n_groups);
+
 #ifdef __cplusplus
 }
 #endif
