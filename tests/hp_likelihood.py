@@ -30,6 +30,21 @@ Derivations (one term t = -0.5 z^2 of a per-sample sum, z = (y - m) * inv_std, i
     log(ln10_d (b - a)): 2 u |log x| + 2.5 u (b - a, the literal ln10_d = ln 10 (1 + u/2), the product) + 2 u |log(...)| +
     u |v|; normal -0.5 ((x - a) / b)^2 - log(b sqrt(2 pi)_d): 5 u |0.5 z^2| + 1.5 u + 2 u |log(...)| + u |v|; the ndim
     values are summed in a chain: gamma_ndim sum |v|.
+
+j_ion records at several sweep radii (JMODE 8 / 9: pem_coupled_system_{loglik,predict}_radii_f64_dev), `radii_record_ref`:
+  * the device forms the record's value as fma(base(r), fma(w, g[k+1] - g[k], g[k]), j_cex(r)) from the radius-free shape g;
+    the reference states the same quantity from the pinned fp64 oracle's own terms (oracle_ctypes.plume_terms with the list of
+    radii): the node value v_k = X1 exp(-(alpha_k / a1)^2) + X2 exp(-(alpha_k / a2)^2) + j_cex at the record's radius, alpha_k =
+    k (pi/2) / 90 and alpha_90 = pi/2 (the doubles of the kernels' grid), in long double, and the model value
+    v_k + w (v_{k+1} - v_k).  A sample the oracle flags invalid over ALL radii is 1e-20 at every record, exactly.
+  * what a correct fp64 evaluation of a node may differ by is the project's j_ion rule and nothing new (tests/parity_rules.py,
+    derived there): s_k = 1e-10 |v_k| + TAU sum |t_i| + 8 eps (1 + |decay|) |I_B0| / (2 pi r^2), the allowance
+    parity_rules.j_ion_error applies to one entry with the term sizes of parity_rules.plume_bounds.  The prediction is a convex
+    combination of two nodes (w in [0, 1]), so their errors combine as (1 - w) s_k + w s_{k+1}; the interpolation's own two
+    roundings add model_error(w, v_k, v_{k+1}).  The 1e-20 fill is exact: slack 0.  Where the oracle's own terms are not finite
+    the slack is not either and nothing is held but the kind of the value (NaN, +inf, -inf), as j_ion_error does.
+  * a long double carries exponents a double does not: a term whose double exp() is exactly zero (argument below -745.13) is
+    zero in the reference as well, so that an infinite amplitude times it is the NaN every fp64 evaluation gives, not inf.
 """
 from fractions import Fraction
 
@@ -119,6 +134,84 @@ def profile_sum(prof, k, w, y, inv_std, valid=None):
     n = valid.sum(axis=-1)
     bound = 1.01 * (n + 6) * U * np.abs(t).sum(axis=-1) + 1.01 * np.where(valid, np.abs(z) * np.abs(st) * dm, LD(0)).sum(axis=-1)
     return t.sum(axis=-1), bound
+
+
+# ---- j_ion records at several sweep radii ---------------------------------------------------------------------------------
+def _radii_nodes(terms, invalid, k, ridx, slack_tab):
+    """(v, s): the long-double node values v_k at angle nodes k and radius indices ridx (integer arrays that broadcast against
+    (n, 1)) and their allowances s_k, slack_tab the (n, 91, R) table parity_rules.plume_bounds(...)['j_slack']"""
+    import parity_rules as pr
+    n = terms['a1'].shape[0]
+    k, ridx = np.broadcast_arrays(np.asarray(k, dtype=np.int64), np.asarray(ridx, dtype=np.int64))
+    shape = np.broadcast_shapes(k.shape, (n, 1))
+    k, ridx = np.broadcast_to(k, shape), np.broadcast_to(ridx, shape)
+    rows = np.arange(n)[:, None]
+    alpha = pr.angle_grid()[k]                                     # the doubles k (pi/2) / 90, and pi/2 itself at k = 90
+    bad = np.asarray(invalid, dtype=bool)[:, None]
+    with np.errstate(all='ignore'):
+        v = _ld(terms['j_cex'])[rows, ridx]
+        for X, a in (('X1', 'a1'), ('X2', 'a2')):
+            u = _ld(alpha) / _ld(terms[a])[:, None]
+            g = np.exp(-(u * u))
+            g = np.where(np.exp(-(alpha / terms[a][:, None]) ** 2) == 0.0, LD(0), g)     # (module docstring, last bullet)
+            v = v + _ld(terms[X])[rows, ridx] * g
+        v = np.where(bad, LD(1e-20), v)
+        s = LD(pr.TOL) * np.abs(v) + _ld(slack_tab[rows, k, ridx])
+        s = np.where(bad, LD(0), s)
+    return v, s
+
+
+def radii_node_values(terms, invalid, *, I_B0):
+    """(v, s) [n][91][R]: every node value of every radius and its allowance (the whole profile oracle_ctypes.plume(...,
+    radii=...)['j_ion'] states in fp64)"""
+    import parity_rules as pr
+    R = terms['X1'].shape[1]
+    slack = pr.plume_bounds(terms, I_B0)['j_slack']
+    v, s = zip(*(_radii_nodes(terms, invalid, np.arange(91)[None, :], np.full((1, 91), r), slack) for r in range(R)))
+    return np.stack(v, axis=-1), np.stack(s, axis=-1)
+
+
+def radii_record_ref(terms, invalid, k, w, ridx, *, I_B0):
+    """(model, slack) [n][n_rec] of j_ion records {k, w, ridx} (arrays that broadcast against (n, n_rec)): the long-double
+    model value v_k + w (v_{k+1} - v_k) at radius ridx of samples whose oracle terms are `terms` (oracle_ctypes.plume_terms
+    with the radii) and whose all-radii flag is `invalid`, and the slack of the module docstring.  I_B0 (n,): the beam current
+    the terms were made with (parity_rules.plume_bounds scales the j_cex floor by it)."""
+    import parity_rules as pr
+    slack_tab = pr.plume_bounds(terms, I_B0)['j_slack']
+    k = np.asarray(k, dtype=np.int64)
+    lo, s_lo = _radii_nodes(terms, invalid, k, ridx, slack_tab)
+    hi, s_hi = _radii_nodes(terms, invalid, k + 1, ridx, slack_tab)
+    wl = np.broadcast_to(_ld(w), lo.shape)
+    with np.errstate(all='ignore'):
+        model = lo + wl * (hi - lo)
+        slack = (LD(1) - wl) * s_lo + wl * s_hi + model_error(wl, lo, hi)
+    bad = np.broadcast_to(np.asarray(invalid, dtype=bool)[:, None], lo.shape)
+    return np.where(bad, LD(1e-20), model), np.where(bad, LD(0), slack)
+
+
+def assert_model_within(got, want, slack, what=''):
+    """`got` against (want, slack) of radii_record_ref: the kind of every value (finite, NaN, +inf, -inf) identical; every
+    finite value with a finite slack inside it.  Returns the largest |got - want| / slack among those (what the slack is used
+    to, for a measurement; 0 where nothing was held)."""
+    got = np.asarray(got, dtype=np.float64)
+    want, slack = np.asarray(want, dtype=LD), np.asarray(slack, dtype=LD)
+    assert got.shape == want.shape == slack.shape, (what, got.shape, want.shape, slack.shape)
+    w64 = want.astype(np.float64)                                   # (a long double past the double range is an fp64 inf)
+    kind = lambda a: np.where(np.isnan(a), 2, np.where(np.isinf(a), np.sign(a), 0))      # noqa: E731
+    with np.errstate(all='ignore'):
+        differ = kind(got) != kind(w64)
+        if differ.any():
+            i = np.unravel_index(np.argmax(differ), differ.shape)
+            raise AssertionError(f'{what}: {int(differ.sum())} values of the wrong kind; first at {i}: got {got[i]!r} want {w64[i]!r}')
+        held = np.isfinite(w64) & np.isfinite(slack)
+        err = np.where(held, np.abs(got.astype(LD) - want), LD(0))
+        bad = held & (err > slack)
+        ratio = np.where(held & (slack > 0), err / np.where(slack > 0, slack, LD(1)), LD(0))
+    if bad.any():
+        i = np.unravel_index(np.argmax(np.where(bad, err / np.maximum(slack, LD(1e-300)), LD(0))), err.shape)
+        raise AssertionError(f'{what}: {int(bad.sum())} values outside the slack; worst at {i}: got {got[i]!r} want {w64[i]!r} '
+                             f'err {float(err[i]):.3e} slack {float(slack[i]):.3e}')
+    return float(ratio.max(initial=0.0))
 
 
 # ---- marginal ---------------------------------------------------------------------------------------------------------

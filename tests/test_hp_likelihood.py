@@ -4,6 +4,7 @@ from fractions import Fraction
 
 import mpmath
 import numpy as np
+import pytest
 
 import hp_likelihood as hl
 
@@ -78,6 +79,90 @@ def test_a_planted_record_error_breaks_the_bound_by_orders_of_magnitude():
         assert np.all(err > 1e6 * bound)
     honest = t.sum(axis=1)
     hl.assert_within(honest, want, bound, 'the same sum in double')
+
+
+PLUME_IN = ('P_b', 'c0', 'c1', 'c2', 'c3', 'c4', 'c5', 'sigma_cex')
+
+
+def _oracle_radii(x, radii):
+    """(terms, I_B0, plume) of the oracle for a dict of the 15 input arrays at the given sweep radii"""
+    from hallthrusterpem_amd import constants
+    from oracle import oracle_ctypes as oc
+    with np.errstate(all='ignore'):
+        I_B0 = oc.coupled(x, constants.TORR_2_PA)['I_B0']
+        args = [x[q] for q in PLUME_IN] + [I_B0, constants.TORR_2_PA]
+        return oc.plume_terms(*args, radii=radii), I_B0, oc.plume(*args, radii=radii)
+
+
+def _host_draws(priors, n, seed):
+    """n draws of a prior table with numpy (the device designs need a GPU)"""
+    from hallthrusterpem_amd import sampling
+    rng = np.random.default_rng(seed)
+    x = {}
+    for name, p in priors.items():
+        if p.kind == sampling.NORMAL:
+            x[name] = rng.normal(p.a, p.b, n)
+        else:
+            v = rng.uniform(p.a, p.b, n)
+            x[name] = 10.0 ** v if p.kind == sampling.LOGUNIFORM else v
+    return x
+
+
+@pytest.mark.parametrize('R', [2, 3, 8])
+def test_radii_reference_agrees_with_the_oracle_on_prior_draws_and_every_pair_is_comparable(R):
+    """the long-double node values of radii_record_ref against the oracle's multi-radius profile under the reference's own
+    slack; parity_rules' `comparable` mask is all true under the priors, so a GPU test may hold div_angle and T_c of every
+    sample (tests/test_likelihood_radii_kernels.py does)"""
+    import parity_rules as pr
+    from _inputs import coupled_inputs
+    radii = tuple(np.linspace(0.4, 1.6, R))
+    terms, I_B0, pl = _oracle_radii(coupled_inputs(2000, seed=40 + R), radii)
+    assert not pl['invalid'].any() and np.isfinite(pl['j_ion']).all()
+    v, s = hl.radii_node_values(terms, pl['invalid'], I_B0=I_B0)
+    assert v.shape == s.shape == (2000, 91, R) and (s > 0).all()
+    worst = hl.assert_model_within(pl['j_ion'], v, s, f'oracle profile at {R} radii, prior draws')
+    print(f'\nR = {R}: oracle against the long-double nodes, worst |diff| / slack = {worst:.3e}')
+    assert pr.plume_bounds(terms, I_B0)['comparable'].all()
+    # the record form at the nodes themselves (w = 0 and w = 1) is the node table
+    k = np.array([[0, 17, 89, 89]])
+    m, sl = hl.radii_record_ref(terms, pl['invalid'], k, np.array([[0.0, 0.0, 0.0, 1.0]]), np.array([[0, R - 1, 1, R - 1]]), I_B0=I_B0)
+    assert np.array_equal(m[:, :3], np.stack([v[:, 0, 0], v[:, 17, R - 1], v[:, 89, 1]], axis=1))
+    assert np.array_equal(m[:, 3], v[:, 90, R - 1])
+    assert np.all(sl[:, 3] >= s[:, 90, R - 1]) and np.all(sl[:, 3] <= s[:, 90, R - 1] * (1 + 1e-5))
+
+
+@pytest.mark.parametrize('negative_density', [False, True])
+@pytest.mark.parametrize('R', [2, 3, 8])
+def test_radii_reference_agrees_with_the_oracle_on_wide_prior_draws(R, negative_density):
+    """outside the priors -- c0 outside [0, 1], negative flow rates, a CEX cross-section down to zero, negative densities whose
+    exp(+x) overflows: invalid samples are 1e-20 throughout, the NaN / inf patterns identical, every other value inside the slack"""
+    from wild_parity import wide_priors
+    radii = tuple(np.linspace(0.4, 1.6, R))
+    terms, I_B0, pl = _oracle_radii(_host_draws(wide_priors(negative_density), 2000, seed=50 + R), radii)
+    assert pl['invalid'].any() and not pl['invalid'].all()
+    if negative_density:
+        assert not np.isfinite(pl['j_ion']).all()
+    v, s = hl.radii_node_values(terms, pl['invalid'], I_B0=I_B0)
+    assert np.all(v[pl['invalid']] == 1e-20) and np.all(s[pl['invalid']] == 0)
+    worst = hl.assert_model_within(pl['j_ion'], v, s, f'oracle profile at {R} radii, wide priors')
+    print(f'\nR = {R}, negative density {negative_density}: worst |diff| / slack = {worst:.3e}')
+
+
+def test_radii_record_slack_catches_a_record_read_at_the_wrong_radius_or_node():
+    """the slack is 1e-10 of the value: the neighbouring radius and the neighbouring node miss it by orders of magnitude"""
+    from _inputs import coupled_inputs
+    radii = (0.4, 1.0, 1.6)
+    terms, I_B0, pl = _oracle_radii(coupled_inputs(300, seed=7), radii)
+    k, w = np.array([[3, 40, 80]]), np.array([[0.25, 0.5, 0.75]])
+    want, slack = hl.radii_record_ref(terms, pl['invalid'], k, w, np.array([[1, 1, 1]]), I_B0=I_B0)
+    j = pl['j_ion']
+    honest = j[:, k[0], 1] + w * (j[:, k[0] + 1, 1] - j[:, k[0], 1])
+    hl.assert_model_within(honest, want, slack, 'the interpolated oracle profile')
+    other_radius = j[:, k[0], 0] + w * (j[:, k[0] + 1, 0] - j[:, k[0], 0])
+    assert np.all(np.abs(other_radius.astype(hl.LD) - want) > 1e9 * slack)
+    # (in the wings a narrow beam has vanished and the profile is the flat j_cex: the next node is told apart inside the beam)
+    next_node = j[:, k[0] + 1, 1] + w * (j[:, k[0] + 2, 1] - j[:, k[0] + 1, 1])
+    assert np.all(np.abs(next_node.astype(hl.LD) - want)[:, :2] > 1e2 * slack[:, :2])
 
 
 def test_marginal_bound_is_finite_with_some_minus_inf_draws_and_catches_a_miscount():
