@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The sampler of examples/calibration_start.py step 4 with nothing left on the host: calibration.DeviceDRAM on one MI355X.
+"""The sampler of examples/calibration_start.py step 4 with nothing left on the host: samplers.DeviceDRAM on one MI355X.
 
   1. the synthetic V_cc, thrust, ion velocity and ion current density data of calibration_start.py (theta* plus 2 % noise);
   2. MAP by differential evolution and the Laplace approximation there, as steps 2 and 3 of that example;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sampling without a proposal covariance: calibration.DeviceEnsemble (the affine-invariant ensemble sampler) on one MI355X.
+"""Sampling without a proposal covariance: samplers.DeviceEnsemble (the affine-invariant ensemble sampler) on one MI355X.
 
   1. the synthetic V_cc, thrust, ion velocity and ion current density data of calibration_start.py (theta* plus 2 % noise);
   2. where the walkers start: the final population of a differential-evolution MAP search (default: it already has the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Calibration without a start: calibration.DeviceSMC (tempered sequential Monte Carlo) on one MI355X.
+"""Calibration without a start: samplers.DeviceSMC (tempered sequential Monte Carlo) on one MI355X.
 
   1. a closed form with two modes -- 0.3 N((-5, 0), I) + 0.7 N((5, 0), I) as the likelihood, a uniform prior on [-15, 15]^2 -- from
      Sobol' draws of the prior: no start, no covariance, no ladder.  The particles at beta = 1 are equally weighted posterior

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A posterior with more than one mode: calibration.DeviceTemperedEnsemble (replica exchange over the ensemble sampler) on one
+"""A posterior with more than one mode: samplers.DeviceTemperedEnsemble (replica exchange over the ensemble sampler) on one
 MI355X.
 
   1. a closed form with two modes -- 0.3 N((-5, 0), I) + 0.7 N((5, 0), I) as the likelihood, a uniform prior on [-15, 15]^2 --

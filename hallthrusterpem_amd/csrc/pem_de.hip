@@ -20,6 +20,7 @@
 #include "pem_common.h"
 #include "pem_hip.h"
 #include "pem_philox.h"
+#include "pem_search.h"
 
 namespace {
 
@@ -41,17 +42,8 @@ struct DeTable {
 using pem::Philox4;
 using pem::philox4x32_10;
 using pem::u53;
-
-// out of line, as in the sampler: the library exp / normcdfinv bodies would otherwise be inlined at every call site
-__device__ __attribute__((noinline)) double transform_call(int kind, double a, double b, double u) {
-    return pem::transform(kind, a, b, u);
-}
-
-// (2k + 1) 2^-53 for a 52-bit k: strictly inside (0, 1), so a normal prior never maps to +-inf
-__device__ __forceinline__ double u_open(uint32_t hi, uint32_t lo) {
-    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-    return (double)(2 * k + 1) * 0x1.0p-53;
-}
+using pem::u_open;
+using pem::search::transform_call;
 
 // an integer in [0, n) from one 32-bit word (multiply-high)
 __device__ __forceinline__ int below(uint32_t w, int n) { return (int)(((uint64_t)w * (uint32_t)n) >> 32); }

@@ -37,11 +37,8 @@ using pem::Philox4;
 using pem::philox4x32_10;
 using pem::u53;
 
-// a standard normal from (2k + 1) 2^-53 for a 52-bit k: strictly inside (0, 1), never +-inf
-__device__ __forceinline__ double normal_of(uint32_t hi, uint32_t lo) {
-    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-    return normcdfinv((double)(2 * k + 1) * 0x1.0p-53);
-}
+// a standard normal from pem::u_open: never +-inf
+__device__ __forceinline__ double normal_of(uint32_t hi, uint32_t lo) { return normcdfinv(pem::u_open(hi, lo)); }
 
 struct Normals {
     double z1, z2;

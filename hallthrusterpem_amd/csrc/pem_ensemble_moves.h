@@ -20,12 +20,9 @@ constexpr uint32_t PURPOSE_PROPOSE = 0x454E0001u;
 constexpr uint32_t PURPOSE_ACCEPT = 0x454E0002u;
 constexpr uint32_t PURPOSE_SWAP = 0x454E0003u;   // replica exchange only (pem_tempering.hip)
 
-// a standard normal from (2k + 1) 2^-53 for a 52-bit k: strictly inside (0, 1), never +-inf.  Out of line, a leaf: with the
-// library normcdfinv body inlined into the propose loop the kernel is allocated 418 vector registers instead of 56.
-static __device__ __attribute__((noinline)) double normal_of(uint32_t hi, uint32_t lo) {
-    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-    return normcdfinv((double)(2 * k + 1) * 0x1.0p-53);
-}
+// a standard normal from pem::u_open: never +-inf.  Out of line, a leaf: with the library normcdfinv body inlined into the
+// propose loop the kernel is allocated 418 vector registers instead of 56.
+static __device__ __attribute__((noinline)) double normal_of(uint32_t hi, uint32_t lo) { return normcdfinv(u_open(hi, lo)); }
 
 // log(x) that a host restates bit for bit: the argument reduction and the degree-14 polynomial of the freely distributable fdlibm
 // e_log.c (x = 2^k (1 + f), sqrt(2) / 2 < 1 + f < sqrt(2); s = f / (2 + f); log(1 + f) = f - (f^2 / 2 - s (f^2 / 2 + R(s^2)))),

@@ -36,6 +36,12 @@ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
     return (double)((((uint64_t)(hi >> 5)) << 26) | (uint64_t)(lo >> 6)) * 0x1.0p-53;
 }
 
+// (2k + 1) 2^-53 for a 52-bit k: strictly inside (0, 1), so a normal prior or normcdfinv never gives +-inf
+__device__ __forceinline__ double u_open(uint32_t hi, uint32_t lo) {
+    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
+    return (double)(2 * k + 1) * 0x1.0p-53;
+}
+
 // products and sums rounded separately (no FMA) so that a host restatement reproduces the design bit for bit
 __device__ __forceinline__ double transform(int kind, double a, double b, double u) {
 #pragma clang fp contract(off)

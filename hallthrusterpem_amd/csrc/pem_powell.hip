@@ -20,6 +20,7 @@
 #include "pem_common.h"
 #include "pem_hip.h"
 #include "pem_philox.h"   // pem::transform, the prior transforms (no random numbers are drawn here)
+#include "pem_search.h"
 
 namespace {
 
@@ -47,15 +48,9 @@ struct PowellTable {
     double a[MAX_DIM], b[MAX_DIM], lb[MAX_DIM], ub[MAX_DIM];
 };
 
-// out of line, as in the sampler: the library exp / normcdfinv bodies would otherwise be inlined at every call site
-__device__ __attribute__((noinline)) double transform_call(int kind, double a, double b, double u) {
-    return pem::transform(kind, a, b, u);
-}
-
-// what scipy minimises: g = -f, a NaN f never wins
-__device__ __forceinline__ double cost(double f) { return f == f ? -f : INFINITY; }
-
-__device__ __forceinline__ double clip(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }
+using pem::search::clip;
+using pem::search::cost;
+using pem::search::transform_call;
 
 __device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }
 

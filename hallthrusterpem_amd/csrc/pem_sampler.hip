@@ -16,6 +16,7 @@
 #include "pem_common.h"
 #include "pem_hip.h"
 #include "pem_philox.h"
+#include "pem_search.h"
 
 namespace {
 
@@ -28,11 +29,8 @@ struct DimTable {
 
 using pem::Philox4;
 using pem::philox4x32_10;
-using pem::transform;
 using pem::u53;
-
-// out of line: inlined, the library exp / normcdfinv bodies cost the kernel 438 registers (one wave per SIMD)
-__device__ __attribute__((noinline)) double transform_call(int kind, double a, double b, double u) { return transform(kind, a, b, u); }
+using pem::search::transform_call;   // out of line: inlined, pem::transform costs the kernel 438 registers (one wave per SIMD)
 
 // keyed bijection of [0, n): 4-round Feistel network on 2*h bits with cycle walking (Latin-hypercube strata)
 __device__ __forceinline__ uint64_t feistel_permute(uint64_t i, uint64_t n, int half_bits, uint32_t k0, uint32_t k1,

@@ -49,11 +49,8 @@ using pem::Philox4;
 using pem::philox4x32_10;
 using pem::u53;
 
-// a standard normal from (2k + 1) 2^-53 for a 52-bit k, as pem_dram.hip draws them
-__device__ __forceinline__ double normal_of(uint32_t hi, uint32_t lo) {
-    const uint64_t k = ((uint64_t)(hi >> 6) << 26) | (uint64_t)(lo >> 6);
-    return normcdfinv((double)(2 * k + 1) * 0x1.0p-53);
-}
+// a standard normal from pem::u_open, as pem_dram.hip draws them
+__device__ __forceinline__ double normal_of(uint32_t hi, uint32_t lo) { return normcdfinv(pem::u_open(hi, lo)); }
 
 // z_j of a particle under counter word `word`.  Out of line, a leaf, its result by value (as pem_dram.hip's step_normals):
 // inlined into the batch loops the Philox rounds and the library normcdfinv cost the stage kernel more registers than the 128 a

@@ -23,14 +23,14 @@ csrc/pem_philox.h): log-uniform inputs mutate in log space, normals need no boun
 caller's `f`; with `use_graph` the two are one hipGraph replay.  `f` is what an optimizer compares across rows, so a
 `JionPosterior` / `SystemPosterior` passed here is built with `shared_nuisance=True` (the same nuisance draws in every row).
 """
-import ctypes as C
 import math
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
-from .calibration import capture_graph
+from ._device_loop import RecordedLoop, zeros_on
+from ._marshal import current_stream_ptr, np_ptr, t_ptr
 from .sampling import LOGUNIFORM, NORMAL, PEM_V0_PRIORS, UNIFORM, Design, Prior
 
 STRATEGIES = {'best1bin': _lib.DE_BEST1BIN, 'rand1bin': _lib.DE_RAND1BIN}
@@ -55,6 +55,41 @@ def support(prior: Prior):
     return prior.a - 3.0 * prior.b, prior.a + 3.0 * prior.b
 
 
+class _Search(RecordedLoop):
+    """What the searches share around their launch.  A subclass has `history` (one row per launch, grown here), `reset()` and
+    its `_body`: one launch and f on the points it emitted."""
+
+    def _record_key(self):
+        return (self.history.data_ptr(), self.history.shape[0])
+
+    def _record(self):
+        self.reset()                       # a search starts over around a recording, where a sampler snapshots its state
+        super()._record()
+
+    def _prepare(self, n_launches: int):
+        """history room for n_launches (the graph is recorded again when the buffer moves), then back to the start"""
+        import torch
+        if self.history.shape[0] < n_launches:
+            self.history = torch.full((n_launches,) + tuple(self.history.shape[1:]), math.nan, dtype=torch.float64,
+                                      device=self.device)
+        super()._prepare()
+        self.reset()
+
+    def _search(self, n, check_every: int, first_check: int, finished):
+        """Launch until the host, reading `finished()` after first_check launches and every check_every from there, sees the
+        end, or n launches have run (None: no limit).  Returns (launches run, whether `finished()` ended them)."""
+        c, check, check_every = 0, int(first_check), int(check_every)
+        while n is None or c < n:
+            m = check - c if n is None else min(check, n) - c
+            self.advance(m)
+            c += m
+            if c == check:
+                if finished():
+                    return c, True
+                check += check_every
+        return c, False
+
+
 @dataclass
 class DEResult:
     theta: np.ndarray        # (d,) the best member
@@ -65,7 +100,7 @@ class DEResult:
     history: np.ndarray      # (generations + 1,) best value of the initial population and of every generation
 
 
-class DifferentialEvolution:
+class DifferentialEvolution(_Search):
     """scipy's `differential_evolution(f, bounds, strategy, popsize=15, mutation=(0.5, 1), recombination=0.7, tol=0.01,
     updating='deferred', vectorized=True)` (mcmc.py:214-216), MAXIMISING f, on the device.
 
@@ -103,11 +138,11 @@ class DifferentialEvolution:
             raise ValueError('recombination must be in [0, 1]')
         self.kind, self.a, self.b = _table(self.names, priors)
         self.f, self.strategy, self.mutation, self.cr = f, STRATEGIES[strategy], (lo, hi), float(recombination)
-        self.tol, self.atol, self.seed, self.use_graph = float(tol), float(atol), int(seed), bool(use_graph)
+        self.tol, self.atol, self.seed = float(tol), float(atol), int(seed)
 
         import torch
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        self._init_loop(device, use_graph)
+        z = zeros_on(self.device)
         self.pop_u, self.trial_u, self.theta = z(self.P, self.d), z(self.P, self.d), z(self.P, self.d)
         self.pop_f, self.trial_f = z(self.P), z(self.P)
         self.state, self.record = z(1, dt=torch.int64), z(3)
@@ -115,38 +150,27 @@ class DifferentialEvolution:
         self.u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(
             self.P, device=self.device, method=self.init).T.contiguous()
         self.history = z(0)
-        self._graph = None
 
     def _launch(self, finalize: bool):
         import torch
-        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
-        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        p, ptr = t_ptr, np_ptr
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pem_de_step_f64_dev(
                 self.P, self.d, self.strategy, 1 if finalize else 0, self.seed, self.mutation[0], self.mutation[1], self.cr,
                 self.tol, self.atol, ptr(self.kind), ptr(self.a), ptr(self.b), p(self.pop_u), p(self.pop_f), p(self.trial_u),
                 p(self.trial_f), p(self.theta), p(self.state), p(self.record), p(self.history) if self.history.numel() else None,
-                self.history.numel(), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                self.history.numel(), current_stream_ptr(self.device)))
 
     def _generation(self):
         self._launch(False)
         self.trial_f.copy_(self.f(self.theta))
 
+    _body = _generation
+
     def reset(self):
         """Back to the initial population (the next launch evaluates it)."""
         self.state.zero_()
         self.trial_u.copy_(self.u0)
-
-    def _prepare(self, n_launches: int):
-        """history room for n_launches; the graph is (re)recorded when the history buffer moves"""
-        import torch
-        if self.history.numel() < n_launches:
-            self.history = torch.full((n_launches,), math.nan, dtype=torch.float64, device=self.device)
-            self._graph = None
-        if self.use_graph and self._graph is None:
-            self.reset()
-            self._graph, _ = capture_graph(self._generation, self.device)
-        self.reset()
 
     def run(self, max_generations: int = 1000, check_every: int = 10) -> DEResult:
         """Evaluate the initial population and at most `max_generations` generations after it; every `check_every`
@@ -154,25 +178,16 @@ class DifferentialEvolution:
         import torch
         if max_generations < 0 or check_every < 1:
             raise ValueError('max_generations >= 0 and check_every >= 1')
-        n = int(max_generations) + 1
-        self._prepare(n)
-        converged = False
-        c = 0
-        for c in range(n):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._generation()
-            if c >= 1 and c % check_every == 0 and self.record[2].item() == 1.0:
-                converged = True
-                break
+        self._prepare(int(max_generations) + 1)
+        c, converged = self._search(int(max_generations) + 1, check_every, check_every + 1,
+                                    lambda: self.record[2].item() == 1.0)
         self._launch(True)                     # selection of the last trials; theta = the population's
         rec = self.record.cpu().numpy()
         best = int(rec[1])
         torch.cuda.synchronize(self.device)
         return DEResult(theta=self.theta[best].cpu().numpy(), u=self.pop_u[best].cpu().numpy(), value=float(rec[0]),
-                        generations=c, converged=converged or bool(rec[2] == 1.0),
-                        history=self.history[:c + 1].cpu().numpy())
+                        generations=c - 1, converged=converged or bool(rec[2] == 1.0),
+                        history=self.history[:c].cpu().numpy())
 
 
 # -------------------------------------------------------------------------------------------------------- Nelder-Mead
@@ -241,7 +256,7 @@ class NMResult:
     final_simplex: tuple     # (sim (S, d + 1, d), fsim (S, d + 1)) in search coordinates, best vertex first
 
 
-class NelderMead:
+class NelderMead(_Search):
     """scipy's `minimize(method='Nelder-Mead', bounds=..., options={'adaptive': True, 'xatol': ..., 'fatol': ...})`
     (run_mle's default optimizer, mcmc.py:170-231), MAXIMISING f, for S independent simplices on the device.
 
@@ -300,52 +315,41 @@ class NelderMead:
         self.S = self._starts if sim0 is None else sim0.shape[0]
         self.rows = self.S * (d + 4)
         self.f, self.coef, self.adaptive = f, nm_coefficients(d, adaptive), bool(adaptive)
-        self.xatol, self.fatol, self.seed, self.use_graph = float(xatol), float(fatol), int(seed), bool(use_graph)
+        self.xatol, self.fatol, self.seed = float(xatol), float(fatol), int(seed)
 
         import torch
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._init_loop(device, use_graph)
         if sim0 is None:
             unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
             u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(self.S, device=self.device, method='lhs').T
             sim0 = nm_simplex(u0.cpu().numpy(), self.lb, self.ub)
-        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        z = zeros_on(self.device)
         self.sim0 = torch.as_tensor(sim0, device=self.device)
         self.sim, self.fsim = z(self.S, d + 1, d), z(self.S, d + 1)
         self.cand_x, self.cand_f, self.theta = z(self.S, d + 4, d), z(self.rows), z(self.rows, d)
         self.state = z(self.S, _lib.NM_STATE_WORDS, dt=torch.int64)
         self.history = z(0, self.S)
-        self._graph = None
 
     def _launch(self, finalize: bool):
         import torch
-        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
-        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        p, ptr = t_ptr, np_ptr
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pem_nm_step_f64_dev(
                 self.S, self.d, 1 if finalize else 0, *self.coef, self.xatol, self.fatol, ptr(self.kind), ptr(self.a),
                 ptr(self.b), ptr(self.lb), ptr(self.ub), p(self.sim), p(self.fsim), p(self.cand_x), p(self.cand_f), p(self.theta),
                 p(self.state), p(self.history) if self.history.numel() else None, self.history.shape[0],
-                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                current_stream_ptr(self.device)))
 
     def _iteration(self):
         self._launch(False)
         self.cand_f.copy_(self.f(self.theta))
 
+    _body = _iteration
+
     def reset(self):
         """Back to the initial simplices (the next launch emits their vertices)."""
         self.state.zero_()
         self.sim.copy_(self.sim0)
-
-    def _prepare(self, n_launches: int):
-        """history room for n_launches; the graph is (re)recorded when the history buffer moves"""
-        import torch
-        if self.history.shape[0] < n_launches:
-            self.history = torch.full((n_launches, self.S), math.nan, dtype=torch.float64, device=self.device)
-            self._graph = None
-        if self.use_graph and self._graph is None:
-            self.reset()
-            self._graph, _ = capture_graph(self._iteration, self.device)
-        self.reset()
 
     def run(self, max_iterations=None, check_every: int = 10) -> NMResult:
         """Iterate until every simplex has converged (the host reads `state` every `check_every` launches) or scipy's `nit`
@@ -357,22 +361,15 @@ class NelderMead:
         if m < 1 or check_every < 1:
             raise ValueError('max_iterations >= 1 and check_every >= 1')
         self._prepare(m)
-        c = 0
-        for c in range(m):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._iteration()
-            if c >= 1 and c % check_every == 0 and bool((self.state[:, 3] == 1).all().item()):
-                break
-        self._launch(True)                     # the last values are resolved; theta = every simplex's best vertex
+        c, _ = self._search(m, check_every, check_every + 1, lambda: bool((self.state[:, 3] == 1).all().item()))
+        self._launch(True)                    # the last values are resolved; theta = every simplex's best vertex
         torch.cuda.synchronize(self.device)
         st = self.state.cpu().numpy()
         sim, fsim = self.sim.cpu().numpy(), self.fsim.cpu().numpy()
         value = fsim[:, 0].copy()
         return NMResult(theta=self.theta.view(self.S, self.d + 4, self.d)[:, 0].cpu().numpy(), u=sim[:, 0].copy(), value=value,
                         nit=st[:, 1].copy(), nfev=st[:, 2].copy(), converged=st[:, 3] == 1, operations=st[:, 4:9].copy(),
-                        best=int(np.argmax(value)), history=self.history[:c + 1].cpu().numpy(), final_simplex=(sim, fsim))
+                        best=int(np.argmax(value)), history=self.history[:c].cpu().numpy(), final_simplex=(sim, fsim))
 
 
 # ------------------------------------------------------------------------------------------------------------- Powell
@@ -399,7 +396,7 @@ class PowellResult:
     history: np.ndarray      # (launches, S) best_value after every consumed value
 
 
-class Powell:
+class Powell(_Search):
     """scipy's `minimize(method='Powell', bounds=..., options={'xtol': ..., 'ftol': ...})` (run_mle(optimizer='powell'),
     mcmc.py:170-231), MAXIMISING f, for S independent searches on the device.
 
@@ -457,40 +454,40 @@ class Powell:
                 raise ValueError('direc must be finite')
             direc0 = np.broadcast_to(direc0, (self.S, d, d))
         self.rows = self.S
-        self.f, self.xtol, self.ftol, self.seed, self.use_graph = f, float(xtol), float(ftol), int(seed), bool(use_graph)
+        self.f, self.xtol, self.ftol, self.seed = f, float(xtol), float(ftol), int(seed)
         self._max_iter = 0
 
         import torch
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._init_loop(device, use_graph)
         if u0 is None:
             unit = {k: Prior(UNIFORM, 0.0, 1.0, 'quantile') for k in self.names}
             u0 = Design(priors=unit, names=self.names, seed=self.seed).sample(self.S, device=self.device, method='lhs').T
             u0 = np.clip(u0.cpu().numpy(), self.lb, self.ub)
-        z = lambda *s, dt=torch.float64: torch.zeros(s, dtype=dt, device=self.device)      # noqa: E731
+        z = zeros_on(self.device)
         self.u0 = torch.as_tensor(np.ascontiguousarray(u0), device=self.device)
         self.direc0 = torch.as_tensor(np.array(direc0), device=self.device)               # (a copy: broadcast_to's is read-only)
         self.vec, self.direc, self.scal = z(self.S, _lib.POWELL_VEC_ROWS, d), z(self.S, d, d), z(self.S, _lib.POWELL_SCALARS)
         self.cand_f, self.theta = z(self.S), z(self.S, d)
         self.state = z(self.S, _lib.POWELL_STATE_WORDS, dt=torch.int64)
         self.history = z(0, self.S)
-        self._graph = None
 
     def _launch(self, finalize: int):
         """finalize 0: a step; 1: theta = x; 2: theta = best_x"""
         import torch
-        p = lambda t: C.c_void_p(t.data_ptr())                                              # noqa: E731
-        ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                       # noqa: E731
+        p, ptr = t_ptr, np_ptr
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pem_powell_step_f64_dev(
                 self.S, self.d, int(finalize), self.xtol, self.ftol, self._max_iter, math.sqrt(2.2e-16),
                 0.5 * (3.0 - math.sqrt(5.0)), ptr(self.kind), ptr(self.a), ptr(self.b), ptr(self.lb), ptr(self.ub), p(self.vec),
                 p(self.direc), p(self.scal), p(self.cand_f), p(self.theta), p(self.state),
                 p(self.history) if self.history.numel() else None, self.history.shape[0],
-                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                current_stream_ptr(self.device)))
 
     def _step(self):
         self._launch(False)
         self.cand_f.copy_(self.f(self.theta))
+
+    _body = _step
 
     def reset(self):
         """Back to the starts and the initial directions (the next launch emits the starts)."""
@@ -498,20 +495,13 @@ class Powell:
         self.vec[:, 0].copy_(self.u0)
         self.direc.copy_(self.direc0)
 
+    def _record_key(self):
+        return super()._record_key() + (self._max_iter,)
+
     def _prepare(self, n_launches: int, max_iter: int):
-        """history room for n_launches; the graph is (re)recorded when the history buffer moves or max_iterations changes (it
-        is a kernel argument)"""
-        import torch
-        if self.history.shape[0] < n_launches:
-            self.history = torch.full((n_launches, self.S), math.nan, dtype=torch.float64, device=self.device)
-            self._graph = None
-        if max_iter != self._max_iter:
-            self._max_iter = max_iter
-            self._graph = None
-        if self.use_graph and self._graph is None:
-            self.reset()
-            self._graph, _ = capture_graph(self._step, self.device)
-        self.reset()
+        """`_Search._prepare`; the graph is recorded again when max_iterations changes as well (it is a kernel argument)"""
+        self._max_iter = max_iter
+        super()._prepare(n_launches)
 
     def run(self, max_iterations=None, max_evaluations=None, check_every: int = 50) -> PowellResult:
         """Search until every start has finished -- the ftol test, or `max_iterations` completed iterations -- or has consumed
@@ -529,16 +519,8 @@ class Powell:
         # values (the kernel writes no row past the buffer) and the launches go on until every search has finished.
         n = None if max_evaluations is None else int(max_evaluations) + 1
         self._prepare(1000 * self.d + 1 if n is None else n, 0 if max_iterations is None else int(max_iterations))
-        c = 0
-        while n is None or c < n:
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._step()
-            c += 1
-            if c % check_every == 0 and bool((self.state[:, 3] != 0).all().item()):
-                break
-        self._launch(2)                        # theta = every search's best_x, as f saw it
+        c, _ = self._search(n, check_every, check_every, lambda: bool((self.state[:, 3] != 0).all().item()))
+        self._launch(2)                       # theta = every search's best_x, as f saw it
         best_theta = self.theta.cpu().numpy()
         self._launch(1)                        # theta = every search's x
         torch.cuda.synchronize(self.device)
@@ -684,7 +666,7 @@ class Laplace:
         return self.mean + np.random.default_rng(seed).standard_normal((int(n), self.mean.size)) @ L.T
 
     def dram_start(self):
-        """(theta0, cov0) for `calibration.DRAM`"""
+        """(theta0, cov0) for `samplers.DRAM`"""
         return self.mean.copy(), self.cov.copy()
 
 
