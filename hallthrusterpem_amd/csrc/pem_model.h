@@ -63,7 +63,8 @@ __device__ __forceinline__ ThrusterQoI thruster_stage(double V_a, double V_cc, d
 }
 
 // exp(x) for x <= 0 without the special-case handling of the library exp: 2^n * P(r), P = degree-13
-// Taylor polynomial on |r| <= ln2/2 (truncation 1.3e-17), n applied with v_ldexp_f64 so that results
+// Taylor polynomial on |r| <= ln2/2 (truncation <= 1.3e-17; the whole function within 1 ulp over [-708, 0] -- both asserted by
+// tests/test_tables_host.py, which restates it with an exact fma against mpmath and measures 0.84 ulp), n applied with v_ldexp_f64 so that results
 // below the normal range denormalise and then flush to 0 like exp() does.  Arguments below -800 give 0;
 // a NaN argument gives 0 as well -- callers carry NaN through the beam amplitudes instead.
 __device__ __forceinline__ double exp_nonpos(double x) {
@@ -88,7 +89,8 @@ __device__ __forceinline__ double exp_nonpos(double x) {
     return ldexp(p, (int)n);
 }
 
-// D(a) with u = 1/a^2: polynomial table for |a| >= 0.25, series below, NaN where the reference is NaN.
+// D(a) with u = 1/a^2: polynomial table for |a| >= 0.25, series below, NaN where the reference is NaN.  Relative error, evaluated as
+// here from a double a: at most 4 units of 2^-53, asserted by tests/test_tables_host.py (measured 3.08 = 3.41e-16 at u = 3/8; series 1.89).
 // `poly` points at the 32 x 12 coefficient table (LDS in the fast kernel, global memory otherwise).
 __device__ __forceinline__ double normaliser(double a, double u, const double* poly) {
     int i = (int)(2.0 * u);  // u >= 0; NaN -> 0, +inf saturates
@@ -130,7 +132,8 @@ __device__ __forceinline__ PlumeSetup plume_setup(double P_b, double c1, double 
 // The two divergence integrals as functions of one beam width (tools/gen_tables.py, QPOLY): with
 // f_k = X1 e_k(a1) + X2 e_k(a2) the Simpson sums of plume.py:117-123 are X1 Qd(a1) + X2 Qd(a2) and X1 Qn(a1) + X2 Qn(a2).
 // Region A: |a| >= 0.25, row floor(2u), u = 1/a^2;  region B: QA_MIN <= |a| < 0.25, row NDI + floor(t),
-// t = (|a| - QA_MIN) * QB_SCALE;  x = 2 (t - row) - 1 in both.  Worst relative error 3.8e-16 (generator self-check).
+// t = (|a| - QA_MIN) * QB_SCALE;  x = 2 (t - row) - 1 in both.  Relative error, evaluated as here: Qd at most 4, Qn at most 5 units of
+// 2^-53, asserted by tests/test_tables_host.py (measured 3.72 = 4.13e-16 and 4.12 = 4.57e-16, both in region B; region A 2.66 and 2.22).
 __device__ __forceinline__ void simpson_functionals(const double2* qpoly, double aa, double u, double& qd, double& qn) {
     const bool wide = aa >= 0.25;
     const double t = wide ? 2.0 * u : (aa - PEM_QA_MIN) * PEM_QB_SCALE;
