@@ -3,17 +3,25 @@
 //
 // pem_log10: argument reduction x = 2^e * m, m in [sqrt(1/2), sqrt(2)); log(m) = log(1+f) by the classical
 //   s = f/(2+f) series 2s + 2s^3/3 + ... summed with the published fdlibm minimax coefficients (|error| < 2^-58.45);
-//   log10(x) = e*log10(2) [hi + lo] + log(m)/ln(10).  Held to <= 2 ulp of numpy's log10 over 5e-324 .. 1.8e308
-//   (tests/test_compression.py).  Branch-free: denormals through v_frexp, 0 / negative / inf / NaN by selects.
+//   log10(x) = e*log10(2) [hi + lo] + log(m)/ln(10).  Largest error measured on the device, quotient by v_rcp_f64 as below:
+//   1.81 ulp (constant: 2 ulp).  Branch-free: denormals through v_frexp, 0 / negative / inf / NaN by selects.
 // pem_exp10: n = rint(y*log2(10)), r = y - n*log10(2) [hi + lo], 10^r = exp(r ln10) by a degree-13 Taylor polynomial
 //   (|r ln10| <= ln2/2, truncation 1.3e-17), scaled by 2^n with ldexp; the argument is clamped to [-330, 310] where
-//   ldexp already gives 0 / inf.  Branch-free.
+//   ldexp already gives 0 / inf.  Branch-free.  Largest error measured on the device: 1.27 ulp, and 1.05 units of 2^-1074 where
+//   the result is denormal (constants: 1.5 and 1.5; the library exp10: 1.07 ulp).
 //
 // pem_log10_tab: the same function from a 1024-entry table staged in LDS (tools/gen_log_table.py, csrc/pem_log_table.h):
 //   i = top 10 mantissa bits, r = fma(m, c_i, -1), log10 x = (e - [i < 424]) log10(2) + T_i + r P5(r).  No division, a
 //   degree-5 instead of a degree-7 polynomial, the special cases decided on the high dword with v_cmp_class: ~13 fp64 +
 //   ~12 fp32-rate instructions against ~40 fp64 ones (fp64 VALU issues at half the fp32 rate on this chip: measured 7.5
-//   cycles per wave instruction).  Largest error 1.3 ulp against a 64-bit-mantissa log10 (libm's own: 1.6 ulp).
+//   cycles per wave instruction).  Error bound 1.4 ulp: in the two table entries next to 1 the result is fl(p r), r = x - 1, and
+//   the roundings of the Horner chain, the representation error of A1 and the product add up to 1.304 ulp (derived in
+//   tests/hp_math.py); the largest error found is 1.3001 ulp at 0x1.0024d25b66d4cp+0 (1.02 ulp outside those entries; libm's own
+//   log10: 1.6 ulp).  The 1.3 ulp documented here earlier was the largest of 2.1e7 samples, and too small.
+//
+// The figures are measured against log10l / powl on the device by tools/microbench/pem_math_ulps.hip (profiles/pem_math_r01.txt) and
+// against mpmath on the host by tests/test_log_table_host.py, over the argument sets of tests/hp_math.py, which also holds the
+// constants; tests/test_math_kernels.py holds the device's table log10 and pem_exp10 to their host restatements bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -871,8 +871,11 @@ def check(got, ref, bnd, what='', mixed=False, oracle=None):
     return rep
 
 
-LOG10_TAB_ULPS = 1.3          # pem_math.h's table log10 (csrc/pem_log_table.h): largest error against a 64-bit-significand log10
-LOG10_SERIES_ULPS = 2.0       # pem_math.h's series log10, which literal_sample takes (held to 2 ulp by tests/test_compression.py)
+# pem_math.h's own log10 functions.  LOG10_TAB_ULPS = 1.4: the table log10 (csrc/pem_log_table.h), derived in tests/hp_math.py and held on
+# the host by tests/test_log_table_host.py.  LOG10_SERIES_ULPS = 2.0: the series log10, which literal_sample takes; measured on the device
+# with its v_rcp_f64 quotient by tools/microbench/pem_math_ulps.hip (profiles/pem_math_r01.txt) and held elementwise through the fused
+# latent kernel by tests/test_math_kernels.py::test_series_log10_on_the_literal_path.
+from hp_math import LOG10_SERIES_ULPS, LOG10_TAB_ULPS  # noqa: E402
 
 
 def latent_reference(ref, bnd, basis, log10):
@@ -880,7 +883,7 @@ def latent_reference(ref, bnd, basis, log10):
     the rounding count of the fma chain, 91 u, on sum_k |norm(j_k) B_kr|, plus what the error of each norm(j_k) contributes: b_j(k)
     for norm none; for log10 the ABSOLUTE error b_j / (|j_k| ln 10) + 2 LOG10 u max(|log10 j_k|, log10 2) -- the table log10 assembles
     its result from e log10(2) + T_i + r P(r), parts that are at least log10(2) in size unless e = 0, so near j = 1 its error is
-    absolute; the series log10 of literal_sample has 2 ulp instead of the table's 1.3.  An invalid sample's row is fill * sum_k B_kr."""
+    absolute; the series log10 of literal_sample has 2 ulp instead of the table's 1.4.  An invalid sample's row is fill * sum_k B_kr."""
     B = np.asarray(basis, f64)
     with np.errstate(all='ignore'):
         j, b, _, _ = j_bound(ref, bnd, 0)

@@ -7,19 +7,24 @@ absolute values.  C is derived from the number of roundings a term of the kernel
 |fl(sum x_i) - sum x_i| <= gamma_k sum |x_i|, gamma_k = k u / (1 - k u) <= 1.01 k u for k u < 0.01), whatever the order
 the kernel sums in: a kernel that drops a term, reads a wrong row or applies a wrong norm misses it by orders of magnitude.
 
-Transcendentals add their own error: log10 in the compress kernels is the table version (csrc/pem_math.h), within 1.3 ulp
-of the exact value, i.e. 2.6 u of its magnitude; 10^x (pem_exp10 in the reconstruct kernel, the library exp10 in the fused
-field path) is held to EXP10_REL of its value -- 2 ulp, the elementwise bound tests/test_compression.py holds pem_exp10 to --
-plus the argument's bound scaled by ln 10 (d 10^v = ln 10 * 10^v dv).
+Transcendentals add their own error, E ulp being at most 2 E u of the magnitude.  The constants are tests/hp_math.py's, derived
+or measured there on the host and on the device (profiles/pem_math_r01.txt): log10 in the compress kernels is the table version
+(csrc/pem_math.h), within LOG10_TAB_ULPS = 1.4 ulp of the exact value, i.e. 2.8 u of its magnitude; 10^x is held to EXP10_REL =
+2 EXP10_ULPS u = 3.33e-16 of its value for pem_exp10 (the reconstruct kernel) and to LIB_EXP10_REL = 2 LIB_EXP10_ULPS u for the
+library exp10 (the fused field path), plus the argument's bound scaled by ln 10 (d 10^v = ln 10 * 10^v dv).
 """
 import ctypes as C
 import itertools
 
 import numpy as np
 
+from hp_math import EXP10_ULPS, LIB_EXP10_ULPS, LOG10_TAB_ULPS
+
 LD = np.longdouble
 U = 2.0 ** -53
-EXP10_REL = 4.5e-16
+EXP10_REL = 2.0 * EXP10_ULPS * U            # pem_exp10
+LIB_EXP10_REL = 2.0 * LIB_EXP10_ULPS * U    # the library exp10
+LOG10_TAB_REL = 2.0 * LOG10_TAB_ULPS        # in units of u
 LN10 = 2.302585092994045684
 NORMS = {'none': 0, 'log10': 1, 'linear': 2}
 assert np.finfo(LD).nmant >= 63, 'the reference needs an 80-bit long double'
@@ -39,30 +44,31 @@ def compress_ref(y, basis, norm, scale=1.0):
     C: each latent is a sum of dof products.  The direct kernel sums them on the matrix pipe (24 MFMA steps of four products
     in two chains, then one add), the tiled kernels in an fma chain of ceil(dof / KG) steps per k-group and log2(KG) shuffle
     adds: no term goes through more than dof + 1 roundings, so the product costs 1.01 (dof + 1) <= dof + 4 for dof <= 208.
-    The norm: linear is one multiplication (1 u of |norm(y)|), log10 the table version (2.6 u of |norm(y)|); each enters
+    The norm: linear is one multiplication (1 u of |norm(y)|), log10 the table version (LOG10_TAB_REL = 2.8 u of |norm(y)|); each enters
     the sum weighted by |basis|, hence the same S."""
     yn = norm_ld(y, norm, scale)
     b = np.asarray(basis, dtype=np.float64).astype(LD)
     z = yn @ b
     s = np.abs(yn) @ np.abs(b)
     dof = b.shape[0]
-    c = dof + 4 + {'none': 0.0, 'linear': 1.0, 'log10': 2.6}[norm]
+    c = dof + 4 + {'none': 0.0, 'linear': 1.0, 'log10': LOG10_TAB_REL}[norm]
     return z, c * U * s
 
 
-def denorm_bound(v, s_v, c_v, norm, scale=1.0):
-    """(field, bound) for field = denorm(v) where v (long double) was formed with at most c_v roundings per term of S = s_v."""
+def denorm_bound(v, s_v, c_v, norm, scale=1.0, exp10_rel=EXP10_REL):
+    """(field, bound) for field = denorm(v) where v (long double) was formed with at most c_v roundings per term of S = s_v;
+    exp10_rel: the relative error of the 10^x the kernel calls."""
     dv = 1.01 * c_v * U * s_v
     if norm == 'log10':
         f = LD(10.0) ** v
-        return f, np.abs(f) * (1.01 * LN10 * dv + EXP10_REL)
+        return f, np.abs(f) * (1.01 * LN10 * dv + exp10_rel)
     if norm == 'linear':
         f = v / LD(scale)
         return f, dv / abs(scale) + U * np.abs(f)
     return v, dv
 
 
-def reconstruct_ref(latent, basis, norm, scale=1.0):
+def reconstruct_ref(latent, basis, norm, scale=1.0, exp10_rel=EXP10_REL):
     """(field, bound) for field = denorm(latent @ basis^T), latent [n][r], basis [dof][r].
 
     C: each value is a sum of r products on the matrix pipe (ceil(r / 4) MFMA steps of four; the zero-padded columns add
@@ -70,13 +76,13 @@ def reconstruct_ref(latent, basis, norm, scale=1.0):
     lat = np.asarray(latent, dtype=np.float64).astype(LD)
     b = np.asarray(basis, dtype=np.float64).astype(LD)
     v = lat @ b.T
-    return denorm_bound(v, np.abs(lat) @ np.abs(b).T, b.shape[1], norm, scale)
+    return denorm_bound(v, np.abs(lat) @ np.abs(b).T, b.shape[1], norm, scale, exp10_rel)
 
 
 def field_ref(latent, basis, norm, scale=1.0):
     """the fused reconstruction of pem_sparse_predict_field_f64_dev: an fma chain over the rank (r roundings), then the
-    denorm -- the same bound as reconstruct_ref"""
-    return reconstruct_ref(latent, basis, norm, scale)
+    denorm -- the same bound as reconstruct_ref, with the library exp10 in the place of pem_exp10"""
+    return reconstruct_ref(latent, basis, norm, scale, LIB_EXP10_REL)
 
 
 def assert_within(got, want, bound, what=''):

@@ -9,7 +9,8 @@ Method (Tang-style table look-up instead of the division + degree-7 series of pe
   with low_i = [i < 424] (m < ~sqrt(1/2): the interval is then read as part of [1, sqrt 2) of the next binade down, so
   that results near x = 1 never come from cancelling e log10(2) against a table value), T_i = -log10(c_i) (+ log10(2)
   for low_i) computed in 40 digits FROM THE ROUNDED c_i, so that the identity above is exact up to the polynomial (and c_i
-  picked, Gal-style, among the doubles within 600 ulp of 1/centre so that T_i is a double to within 1e-3 ulp), and the
+  picked, Gal-style, among the doubles within 600 ulp of 1/centre so that T_i is as close to a double as those 1201 candidates
+  allow: the search stops at 2^-10 ulp where it finds that, and otherwise keeps the best, 0.059 ulp in the worst entry), and the
   two entries next to x = 1 pinned to c = 2 (i = 0) and c = 1 (i = 1023) with T = 0: there r = x - 1 exactly and the
   result keeps full relative accuracy.  log1p(r)/ln 10 = r (a1 + r (a2 + ... + r a6)), a_k = (-1)^(k+1) / (k ln 10):
   truncation r^7 / 7 < 2^-62 |r|.
@@ -17,8 +18,12 @@ Method (Tang-style table look-up instead of the division + degree-7 series of pe
 Self-check: compiles the same algorithm in C (libm fma = the device's v_fma_f64) and compares it with libm's log10 on
 2e7 arguments (log-uniform over the whole range, denormals, a dense sweep around 1, every interval edge): the largest
 error against log10l (x87 extended, 64-bit mantissa) is printed and must be <= 1.5 ulp (libm's own is printed beside it).
+The bound itself, 1.4 ulp, is derived in tests/hp_math.py; tests/test_log_table_host.py holds the committed header to mpmath entry
+by entry, tools/microbench/pem_math_ulps.hip measures the device (profiles/pem_math_r01.txt).
 
-Run:  python tools/gen_log_table.py   (rewrites the header; the header is committed)
+Run:  python tools/gen_log_table.py           (rewrites the header; the header is committed)
+      python tools/gen_log_table.py --check   (writes nothing: regenerates in memory, compares with the committed header byte for
+                                               byte and runs the C self-check on it; exit status 0 if both hold)
 """
 import subprocess
 import sys
@@ -80,7 +85,7 @@ int main(void) {
 '''
 
 
-def main():
+def main(check=False):
     mp.mp.dps = 40
     rows = []
     worst_miss = 0.0
@@ -93,7 +98,8 @@ def main():
             c = 1.0
         else:
             # Gal's accurate tables: among the doubles within 600 ulp of 1/centre (r barely moves) take the one whose
-            # T_i lies closest to a double -- within 2^-9 ulp or better -- so that rounding T_i costs nothing
+            # T_i lies closest to a double -- 0.059 ulp in the worst entry, 2^-10 ulp where the search stops early -- so that
+            # rounding T_i costs next to nothing
             c0 = float(1 / centre)
             best = (1.0, c0)
             c = float(np.nextafter(c0, 0.0))
@@ -133,8 +139,15 @@ def main():
     for i in range(0, N, 2):
         lines.append('    ' + ', '.join(f'{c.hex()}, {t.hex()}' for c, t in rows[i:i + 2]) + ',')
     lines.append('};')
-    OUT.write_text('\n'.join(lines) + '\n')
-    print(f'wrote {OUT} ({N} entries, {16 * N} bytes); every T_i within {worst_miss:.1e} ulp of its double')
+    text = '\n'.join(lines) + '\n'
+    if check:
+        same = OUT.read_text() == text
+        print(f'{OUT}: {"identical to" if same else "DIFFERS from"} the regenerated header; every T_i within {worst_miss:.1e} ulp of its double')
+        if not same:
+            return 1
+    else:
+        OUT.write_text(text)
+        print(f'wrote {OUT} ({N} entries, {16 * N} bytes); every T_i within {worst_miss:.1e} ulp of its double')
     with tempfile.TemporaryDirectory() as tmp:
         src = Path(tmp) / 'check.c'
         src.write_text(CHECK_C)
@@ -147,4 +160,4 @@ def main():
 
 
 if __name__ == '__main__':
-    sys.exit(main())
+    sys.exit(main(check='--check' in sys.argv[1:]))
