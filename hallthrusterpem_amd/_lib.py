@@ -25,6 +25,9 @@ DE_BEST1BIN, DE_RAND1BIN = 0, 1     # PEM_DE_*: its strategies
 NM_MAX_DIM, NM_STATE_WORDS = 32, 10   # PEM_NM_MAX_DIM / PEM_NM_STATE_WORDS: dimensions and state words per simplex of pem_nm_step_f64_dev
 POWELL_MAX_DIM, POWELL_STATE_WORDS = 32, 24   # PEM_POWELL_MAX_DIM / PEM_POWELL_STATE_WORDS: the same of pem_powell_step_f64_dev, per search
 POWELL_SCALARS, POWELL_VEC_ROWS = 20, 6       # PEM_POWELL_SCALARS / PEM_POWELL_VEC_ROWS: its doubles and d-vectors per search
+DIRECT_MAX_DIM, DIRECT_MAX_LEVELS, DIRECT_MAX_DEPTH = 32, 1024, 64   # PEM_DIRECT_MAX_DIM / _MAX_LEVELS / _MAX_DEPTH: dimensions, level-table entries and exponents of pem_direct_step_f64_dev
+DIRECT_MAX_ROWS, DIRECT_MAX_STORE = 1024, 16777216   # PEM_DIRECT_MAX_ROWS / _MAX_STORE: rows per launch and rectangles of its store
+DIRECT_STATE_WORDS, DIRECT_HISTORY_COLS = 10, 3      # PEM_DIRECT_STATE_WORDS / _HISTORY_COLS: its state words and the doubles of a history row
 DRAM_MAX_DIM = 32              # PEM_DRAM_MAX_DIM: dimensions of pem_dram_step_f64_dev (one lane per dimension)
 ENSEMBLE_MAX_DIM, ENSEMBLE_MAX_WALKERS = 32, 1024   # PEM_ENSEMBLE_MAX_DIM / _MAX_WALKERS: dimensions and walkers per ensemble of pem_ensemble_step_f64_dev
 SMC_MAX_DIM, SMC_MAX_PARTICLES, SMC_BISECTIONS = 32, 16384, 52   # PEM_SMC_*: dimensions, particles per population and ESS halvings of pem_smc_stage_f64_dev
@@ -143,6 +146,8 @@ SIGNATURES = {
                                       _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
     'pem_nm_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _f8, _f8, _f8, _f8, _f8, _f8] + [_dp] * 12 + [_sz, _dp]),
     'pem_powell_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _f8, _f8, C.c_uint64, _f8, _f8] + [_dp] * 12 + [_sz, _dp]),
+    'pem_direct_step_f64_dev': (C.c_int, [C.c_int, C.c_int, _sz, C.c_int, C.c_int, _f8, _f8, _f8, C.c_uint64, C.c_uint64] + [_dp] * 17
+                                          + [_sz, _dp]),
     'pem_dram_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_uint64, _f8, _f8, C.c_uint64, C.c_uint64, C.c_uint64, _sz, C.c_uint64]
                                         + [_dp] * 13 + [_dp]),
     'pem_ensemble_step_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_uint64, _f8, _f8, _f8, _f8, C.c_uint64, _sz, C.c_uint64]

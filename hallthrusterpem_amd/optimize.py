@@ -11,8 +11,9 @@ Restates the steps of scripts/pem_v0/mcmc.py that come before `run_mcmc`:
     run_mle(optimizer='powell')      mcmc.py:170-231   `Powell`: scipy's bounded Powell for S searches at once; a line search wants
                                                        one value at a time, so one launch of csrc/pem_powell.hip advances every
                                                        search by one value and the S points are the rows of ONE posterior launch
-    run_mle(optimizer='direct')      mcmc.py:170-231   not restated: scipy's DIRECT is compiled code whose source is not at hand,
-                                                       so it cannot be restated and pinned the way the other three are
+    run_mle(optimizer='direct')      mcmc.py:170-231   `Direct`: scipy's DIRECT without local bias, pinned through the points it
+                                                       evaluates; its rectangles live on the device and the 2 |I| points of every
+                                                       rectangle a round divides are rows of ONE posterior launch (csrc/pem_direct.hip)
     run_laplace / show_laplace       mcmc.py:234-265  `hessian` (central differences, 2 d^2 + 1 points in one call) and
                                                        `Laplace` (cov = pinv(-H), nearest positive-definite fall-back, draws)
     pdf_slice                        mcmc.py:132-148   `slices`: log prior, likelihood and posterior along every axis
@@ -532,6 +533,159 @@ class Powell(_Search):
                             best_theta=best_theta, best_u=vec[:, 4].copy(), best_value=best_value, direc=self.direc.cpu().numpy(),
                             counters={k: st[:, 8 + j].copy() for j, k in enumerate(POWELL_COUNTERS)},
                             best=int(np.argmax(best_value)), history=self.history[:min(c - 1, self.history.shape[0])].cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------------------------- DIRECT
+DIRECT_STATUS = {0: 'running', 1: 'max_evaluations exceeded', 2: 'max_iterations reached', 4: 'vol_tol met', 5: 'len_tol met',
+                 6: 'the store or the level table cannot hold the next round', 7: 'a value was NaN or infinite'}
+
+
+def direct_tables(d: int):
+    """(thirds (D + 1,), levels (D d,)) of pem_direct_step_f64_dev as the host rounds them, D = the exponents the level table
+    of PEM_DIRECT_MAX_LEVELS entries holds for d dimensions"""
+    n = min(_lib.DIRECT_MAX_LEVELS // d, _lib.DIRECT_MAX_DEPTH)
+    thirds = np.empty(n + 1)
+    thirds[0] = 1.0
+    h = 3.0
+    for i in range(1, n + 1):
+        thirds[i] = 1.0 / h
+        h *= 3.0
+    w = [math.sqrt(d - j + j / 9.) * 0.5 for j in range(d)]
+    levels = np.empty(n * d)
+    h = 1.0
+    for i in range(n):
+        for j in range(d):
+            levels[i * d + j] = w[j] / h
+        h *= 3.0
+    return thirds, levels
+
+
+@dataclass
+class DirectResult:
+    theta: np.ndarray        # (d,) the point of the best centre, as f saw it
+    u: np.ndarray            # (d,) scipy's x in search coordinates: c xs1 + xs1 xs2 (an ulp from the point evaluated)
+    value: float             # f there (scipy's -fun)
+    nit: int                 # scipy's nit
+    nfev: int                # values consumed (scipy's nfev)
+    status: int              # DIRECT_STATUS; 1, 2, 4 and 5 are scipy's
+    launches: int            # launches up to the one that ended the search
+    history: np.ndarray      # (launches - 1, 3) best value, nfev and nit after every launch that consumed values
+
+
+class Direct(_Search):
+    """scipy's `direct(f, bounds, eps=..., vol_tol=..., len_tol=..., locally_biased=False)` (run_mle(optimizer='direct'),
+    mcmc.py:170-231, which passes eps=1), MAXIMISING f, with the rectangles on the device.
+
+    DIRECT needs no start, no covariance and no random numbers, and a selection round asks for the 2 |I| points of every
+    rectangle it divides at once.  One launch of `pem_direct_step_f64_dev` (csrc/pem_direct.hip, one workgroup) takes the values
+    of the rows it emitted last, completes those divisions, selects when the round is over and emits the points of as many
+    selected rectangles as fit into `rows`; those are the rows of ONE call of f.  The search runs in the prior's quantile cube,
+    bounded by `search_bounds`; every point, x, fun, nit, nfev and the status are scipy 1.15's bit for bit while no two values
+    tie (include/pem_hip.h says what happens when they do, and which statuses are not scipy's).
+
+    f: callable (rows, d) float64 device tensor -> rows values, like `Powell`'s: `post.log_posterior` of a posterior built with
+       n_chains = direct.rows, shared_nuisance=True and fresh_nuisance=False.  Rows left over in a launch carry the best point
+       and their values are ignored.
+    rows: at least 2 d (one rectangle's points are never split); the smallest multiple of 64 that is if None.
+    use_graph: a step (the launch, f's launches and the copy of the values) is one hipGraph replay on one stream."""
+
+    def __init__(self, f, names, priors=None, rows=None, eps: float = 1e-4, vol_tol: float = 1e-16, len_tol: float = 1e-6,
+                 use_graph: bool = False, device=None, locally_biased: bool = False):
+        self.names = tuple(names)
+        self.d = d = len(self.names)
+        if len(set(self.names)) != d or d < 1:
+            raise ValueError('names must be distinct and non-empty')
+        if d > _lib.DIRECT_MAX_DIM:
+            raise ValueError(f'at most {_lib.DIRECT_MAX_DIM} searched inputs (got {d})')
+        if locally_biased:
+            raise ValueError('locally_biased=True (DIRECT_L) is not restated; run_mle calls direct(..., locally_biased=False)')
+        self.rows = -(-2 * d // 64) * 64 if rows is None else int(rows)
+        if not 2 * d <= self.rows <= _lib.DIRECT_MAX_ROWS:
+            raise ValueError(f'rows must be in [2 d = {2 * d}, {_lib.DIRECT_MAX_ROWS}] (got {self.rows})')
+        if not (0.0 <= eps < math.inf):
+            raise ValueError('eps must be finite and >= 0')
+        if not (0.0 <= vol_tol <= 1.0 and 0.0 <= len_tol <= 1.0):
+            raise ValueError('vol_tol and len_tol must be in [0, 1]')
+        self.kind, self.a, self.b = _table(self.names, priors)
+        self.lb, self.ub = search_bounds(self.names, priors)
+        self.f, self.eps, self.vol_tol, self.len_tol = f, float(eps), float(vol_tol), float(len_tol)
+        self._max_iter, self._max_fun, self.cap = 1000, 1000 * d, 0
+        thirds, levels = direct_tables(d)
+        self.n_depth = thirds.size - 1
+
+        import torch
+        self._init_loop(device, use_graph)
+        z = zeros_on(self.device)
+        self.thirds, self.levels = torch.as_tensor(thirds, device=self.device), torch.as_tensor(levels, device=self.device)
+        self.cand_f, self.theta = z(self.rows), z(self.rows, d)
+        self.queue, self.rowinfo = z(_lib.DIRECT_MAX_LEVELS, dt=torch.int32), z(self.rows, 2, dt=torch.int32)
+        self.state = z(_lib.DIRECT_STATE_WORDS, dt=torch.int64)
+        self.history = z(0, _lib.DIRECT_HISTORY_COLS)
+        self._store(2 * d + 1)
+
+    def _store(self, cap: int):
+        """room for cap rectangles"""
+        import torch
+        if cap != self.cap:
+            z = zeros_on(self.device)
+            self.cap = cap
+            self.centres, self.values = z(cap, self.d), z(cap)
+            self.expo, self.level = z(cap, self.d, dt=torch.int32), z(cap, dt=torch.int32)
+
+    def _launch(self, finalize: bool):
+        import torch
+        p, ptr = t_ptr, np_ptr
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pem_direct_step_f64_dev(
+                self.d, self.rows, self.cap, self.n_depth, 1 if finalize else 0, self.eps, self.vol_tol, self.len_tol,
+                self._max_iter, self._max_fun, ptr(self.kind), ptr(self.a), ptr(self.b), ptr(self.lb), ptr(self.ub),
+                p(self.thirds), p(self.levels), p(self.centres), p(self.values), p(self.expo), p(self.level), p(self.queue),
+                p(self.rowinfo), p(self.cand_f), p(self.theta), p(self.state),
+                p(self.history) if self.history.numel() else None, self.history.shape[0], current_stream_ptr(self.device)))
+
+    def _step(self):
+        self._launch(False)
+        self.cand_f.copy_(self.f(self.theta))
+
+    _body = _step
+
+    def reset(self):
+        """Back to the start (the next launch emits the centre of the cube)."""
+        self.state.zero_()
+
+    def _record_key(self):
+        return super()._record_key() + (self._max_iter, self._max_fun, self.cap, self.centres.data_ptr(), self.values.data_ptr(),
+                                        self.expo.data_ptr(), self.level.data_ptr())
+
+    def run(self, max_iterations: int = 1000, max_evaluations=None, check_every: int = 10) -> DirectResult:
+        """Search until one of scipy's stops: `max_iterations` (its maxiter: the start's division and max_iterations - 2
+        selection rounds), more than `max_evaluations` values after a whole round (its maxfun; None: 1000 d), vol_tol or
+        len_tol.  The store is sized for max_evaluations and one more round; status 6 says it was too small.  The host reads
+        the status every `check_every` launches."""
+        import torch
+        max_evaluations = 1000 * self.d if max_evaluations is None else int(max_evaluations)
+        if max_iterations < 1 or max_evaluations < 1 or check_every < 1:
+            raise ValueError('max_iterations >= 1, max_evaluations >= 1 and check_every >= 1')
+        cap = max_evaluations + 1 + 2 * self.d * _lib.DIRECT_MAX_DEPTH
+        if cap > _lib.DIRECT_MAX_STORE:
+            raise ValueError(f'max_evaluations asks for a store of {cap} rectangles (at most {_lib.DIRECT_MAX_STORE})')
+        self._store(cap)
+        self._max_iter, self._max_fun = int(max_iterations), max_evaluations
+        # every launch after the first stores at least two rectangles or ends the search
+        n = cap // 2 + 3 + int(check_every)
+        self._prepare(n)
+        c, _ = self._search(n, check_every, check_every, lambda: self.state[3].item() != 0)
+        self._launch(True)                      # row 0 of theta = the best centre's point
+        torch.cuda.synchronize(self.device)
+        st = self.state.cpu().numpy()
+        best, end = int(st[6]), int(st[9]) if st[3] != 0 else c
+        xs1 = self.ub - self.lb
+        xs2 = self.lb / xs1
+        centre = self.centres[best].cpu().numpy()
+        return DirectResult(theta=self.theta[0].cpu().numpy(), u=centre * xs1 + xs1 * xs2,
+                            value=-float(self.values[best].item()) if st[2] >= 1 else math.nan,
+                            nit=int(st[1]), nfev=int(st[2]), status=int(st[3]), launches=end,
+                            history=self.history[:max(end - 1, 0)].cpu().numpy())
 
 
 # ----------------------------------------------------------------------------------------------------------- Laplace

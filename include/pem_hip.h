@@ -915,6 +915,71 @@ int pem_powell_step_f64_dev(size_t n_search, int ndim, int finalize, double xtol
                             const double* ub, double* vec, double* direc, double* scal, const double* cand_f, double* theta,
                             uint64_t* state, double* history, size_t history_len, pem_stream_t stream);
 
+/* ---- DIRECT, one search with its rectangles on the device, many values per launch (csrc/pem_direct.hip, optimize.Direct) ----
+ * Stands in for direct(obj_fun, bds, eps=1, maxiter=maxfev, locally_biased=False) of run_mle (scripts/pem_v0/mcmc.py:170-231,
+ * optimizer='direct'): scipy 1.15's DIRECT without local bias, one workgroup, MAXIMISING f over x in [lb, ub]^ndim (g = -f + 0 is
+ * minimised).  A launch takes the values of the rows it emitted last, completes the divisions they belong to, selects when the
+ * round's queue is empty, and emits the points of as many queued rectangles as fit into `rows`; the consumed rows, in order,
+ * are scipy's evaluation sequence.  kind/a/b (the prior table, theta = the prior transform of x) and lb/ub are HOST arrays of ndim.
+ * DEVICE arrays, d = ndim, D = n_depth:
+ *   thirds [D + 1]      thirds[0] = 1, thirds[i] = 1 / h, h = 3 multiplied by 3 after each entry, as the host rounds them
+ *   levels [D d]        levels[i d + j] = w[j] / h, w[j] = sqrt(d - j + j / 9.) * 0.5, h = 1 multiplied by 3 after each i
+ *   centres [cap][d]    the centre c of every rectangle in the unit cube; the point evaluated for it is (c + xs2) xs1 with
+ *                       xs1 = ub - lb, xs2 = lb / xs1, the sum and the product rounded separately
+ *   values [cap]        g at the centre;  expo [cap][d] int32: side i is 3^-expo[i];  level [cap] int32: k d + (d - p) with
+ *                       k = min_i expo[i], p = the sides with expo[i] == k; the rectangle's size measure is levels[level]
+ *   queue [PEM_DIRECT_MAX_LEVELS] int32   the rectangles the current round divides, in ascending level
+ *   rowinfo [rows][2] int32   of the rows emitted last: the rectangle divided (-1 a left-over row, -2 the start's centre) and
+ *                       2 side + (1 for c - delta, 0 for c + delta)
+ *   cand_f [rows]       f of the emitted rows, written by the caller between launches;  theta [rows][d] those rows
+ *   state [PEM_DIRECT_STATE_WORDS]  0 launches, 1 nit, 2 nfev (= the rectangles stored), 3 status, 4 queue head, 5 queue length,
+ *                       6 the lowest index of the lowest g, 7 rows emitted last, 8 ties met (below), 9 the launch counter after the
+ *                       launch that ended the search.  The caller zeroes word 0.
+ *   history [history_len][PEM_DIRECT_HISTORY_COLS] or NULL   after launch l >= 1, row l - 1: the best f, nfev, nit
+ * By the launch counter l = state word 0:
+ *   l == 0  words 1-9 are zeroed; centre 0 = 0.5 in every coordinate is emitted as row 0 (the other rows carry it too); l = 1.
+ *   l >= 1, status 0
+ *     1. consume: g = -cand_f + 0 of the rows emitted last.  One that is not finite: status 7, nothing is stored.  Otherwise
+ *        row r becomes rectangle nfev + r.  A divided rectangle's 2 |I| rows are always in one launch: with k = min expo,
+ *        I = its sides with expo == k ascending and w_i = min(g+, g-), the sides are taken in ascending w (stably); each
+ *        raises expo[i] by one and its two children copy expo as it then is.  The best index moves to the lowest new index of
+ *        the lowest new g when that is strictly below the best g.
+ *     2. when the queue is empty the round has ended.  After the start's value: the queue is rectangle 0.  Otherwise nit += 1
+ *        and, in this order: status 1 when nfev > max_fun; 4 when the product of thirds[expo[i]] of the best rectangle, taken
+ *        in ascending i, is < vol_tol; 5 when its levels[level] < len_tol; 2 when nit + 1 >= max_iter (nit = max(max_iter, 2),
+ *        as scipy reports it: max_iter allows max_iter - 2 selections).  Else the selection: per level the lowest g and the
+ *        lowest index that has it (the anchor); walking the levels upwards an anchor is kept iff its g is strictly below every
+ *        anchor's before it; while more than one is kept, the last kept j is dropped when g_j - lo levels[level_j] > gmin - eps
+ *        |gmin|, lo = the minimum over the kept i before j of (g_i - g_j) / (levels[level_i] - levels[level_j]) -- difference,
+ *        quotient and product rounded separately --, and the pruning ends at the first j that stays.  Status 6 when the kept
+ *        anchors' points do not fit into cap or one of them has k + 2 > n_depth; else they are the queue.
+ *     3. emit: rectangles are popped from the queue while their 2 |I| points fit into the rows left: for i in I ascending
+ *        c + thirds[k + 1] e_i, then c - thirds[k + 1] e_i.  Left-over rows carry the best point; their values are ignored.
+ *   l >= 1, status != 0  frozen: every row is the best point and stays; only l and the history move.
+ *   finalize 1  consumes nothing: row 0 of theta becomes the best centre's point; l is kept.  Nothing happens when l == 0.
+ * Statuses 1, 2, 4 and 5 are scipy's (its f_min stop, 3, is not offered).  Two are not: 6, the store or the level table
+ * cannot hold the next round (scipy allocates what maxfun needs and stops with an error); 7, a value was NaN or infinite
+ * (scipy replaces such points by a rule that is not restated).  Ties -- equal g inside a level, equal w across sides -- are
+ * outside the contract (scipy divides every tied rectangle; here the lowest index wins) and are counted in word 8.
+ * Integer minima in LDS on an order-preserving key of g, no floating-point atomics: the same bits on every run.
+ * Refused with PEM_ERR_INVALID_ARG before the device is looked at: ndim outside [1, PEM_DIRECT_MAX_DIM], rows outside
+ * [2 ndim, PEM_DIRECT_MAX_ROWS], cap outside [2 ndim + 1, PEM_DIRECT_MAX_STORE], n_depth outside [2, PEM_DIRECT_MAX_DEPTH] or
+ * n_depth ndim > PEM_DIRECT_MAX_LEVELS, finalize outside 0 ... 1, eps negative, NaN or infinite, vol_tol or len_tol outside
+ * [0, 1], max_iter 0, a NULL array other than history, lb >= ub or a bound that is not finite, an unknown prior kind, a history
+ * with history_len 0.                                                                                                      */
+#define PEM_DIRECT_MAX_DIM 32
+#define PEM_DIRECT_MAX_LEVELS 1024
+#define PEM_DIRECT_MAX_DEPTH 64
+#define PEM_DIRECT_MAX_ROWS 1024
+#define PEM_DIRECT_MAX_STORE 16777216
+#define PEM_DIRECT_STATE_WORDS 10
+#define PEM_DIRECT_HISTORY_COLS 3
+int pem_direct_step_f64_dev(int ndim, int rows, size_t cap, int n_depth, int finalize, double eps, double vol_tol, double len_tol,
+                            uint64_t max_iter, uint64_t max_fun, const int32_t* kind, const double* a, const double* b,
+                            const double* lb, const double* ub, const double* thirds, const double* levels, double* centres,
+                            double* values, int32_t* expo, int32_t* level, int32_t* queue, int32_t* rowinfo, const double* cand_f,
+                            double* theta, uint64_t* state, double* history, size_t history_len, pem_stream_t stream);
+
 /* ---- delayed-rejection adaptive Metropolis, one launch per step (csrc/pem_dram.hip, calibration.DeviceDRAM) -----------------
  * Stands in for uq.dram(fun, p0, niter, adapt_after, adapt_interval, eps, gamma) of run_mcmc (scripts/pem_v0/mcmc.py:275-300;
  * uqtils is third-party and absent: parity UNPINNED, the algorithm is calibration.DRAM's) for n_chains chains of dimension
