@@ -1293,6 +1293,36 @@ int pem_pairwise_lse_f64_dev(size_t n_out, size_t n_in, int n_col, const double*
                              size_t work_len, pem_stream_t stream);
 size_t pem_pairwise_lse_work_len(size_t n_out, size_t n_in, int n_groups);
 
+/* ---- the conditional term of the information gain about a subset of the inputs (csrc/pem_information_theta.hip,
+ * hallthrusterpem_amd/information.py `about=`): every outer draw's log-mean-exp over its OWN set of predictions, straight from the
+ * output of the system-predict launch.
+ *   z_out [n_out][ld_out]       DEVICE, the standardised observations, n_col <= ld_out columns used
+ *   pred  [n_out n_per][ld_pred] DEVICE, the raw predictions, padding records included; outer row i owns rows i n_per ... (i+1) n_per - 1
+ *   col   [n_col]               DEVICE, nullable (= identity, then n_col <= ld_pred): the record index of column k.  An index outside
+ *                               [0, ld_pred) is not read: the column counts as NaN
+ *   scale [n_col]               DEVICE, nullable (= 1): the factor of column k
+ *   group_end [n_groups]        HOST, as in pem_pairwise_lse_f64_dev; set n_groups is the union of all columns
+ *   lse, ess [n_out][n_groups + 1], used [n_out]   DEVICE
+ * For outer row i, its row l and set c, all in fp64:
+ *   v_k  = fl64(pred[i n_per + l][col[k]] * scale[k])        the product is rounded before the subtraction
+ *   d2_c = sum_{k in c} (z_out[i][k] - v_k)^2                one fma chain in increasing k; the union's d2 is the sum of the groups'
+ *                                                            d2 of the same row, added in group order
+ *   a row is used iff its union d2 is finite (a NaN or inf in one of its columns leaves it out of EVERY set); used[i] counts them
+ *   l = -d2 / 2,  m = max l,  s1 = sum exp(l - m),  s2 = sum exp(l - m)^2   over the used rows
+ *   lse[i][c] = m + log s1 - log used[i]      ess[i][c] = s1^2 / s2;   used[i] = 0 gives NaN for both
+ * The gathered, scaled (n_out n_per, n_col) tensor is never written; pred is read once, a wave load covering 2 rows x
+ * PEM_CONDITIONAL_CHUNK columns.  One workgroup of one wave per outer row walks its rows in tiles of 64 and merges the tiles in
+ * their order: no floating-point atomics, and the bits of row i depend on that row, its n_per rows, col, scale and the groups
+ * only -- not on n_out or the grid.
+ * Refused with PEM_ERR_INVALID_ARG before any device call: a zero size, n_groups outside [1, PEM_INFORMATION_MAX_GROUPS], a null
+ * pointer other than col and scale, ld_out < n_col, ld_pred < 1 (< n_col without col), group_end not strictly ascending from above
+ * 0 or not ending at n_col, n_out n_per ld_pred or n_out ld_out doubles past size_t, n_out or n_per > INT_MAX,
+ * n_col > INT_MAX - PEM_CONDITIONAL_CHUNK.                                                                          */
+#define PEM_CONDITIONAL_CHUNK 32
+int pem_conditional_lse_f64_dev(size_t n_out, size_t n_per, int n_col, const double* z_out, size_t ld_out, const double* pred,
+                                size_t ld_pred, const int* col, const double* scale, int n_groups, const int* group_end, double* lse,
+                                double* ess, int* used, pem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
