@@ -38,6 +38,7 @@ KDE_MAX_GRID, KDE_ROW_BLOCK = 4096, 4096   # PEM_KDE_MAX_GRID / PEM_KDE_ROW_BLOC
 HEX_MAX_GRID, HEX_ROW_TILE = 64, 128       # PEM_HEX_MAX_GRID / PEM_HEX_ROW_TILE: nx, ny and rows per stage of pem_chain_hex_f64_dev
 INFORMATION_MAX_GROUPS = 32                # PEM_INFORMATION_MAX_GROUPS: column groups of pem_pairwise_lse_f64_dev
 INFORMATION_CHUNK, INFORMATION_INNER_BLOCK = 16, 512   # PEM_INFORMATION_CHUNK / _INNER_BLOCK: columns it stages per step, inner rows per workspace partial
+NOISE_MAX_GROUPS = 8                       # PEM_NOISE_MAX_GROUPS: condition groups of pem_loglik_marginal_scaled_f64_dev
 CONDITIONAL_CHUNK = 32                     # PEM_CONDITIONAL_CHUNK: columns pem_conditional_lse_f64_dev stages per step
 
 _dp = C.c_void_p          # every array crosses the boundary as a raw pointer
@@ -81,6 +82,8 @@ SIGNATURES = {
     'pem_predictive_noise_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _sz, _dp]),
     'pem_coupled_latent_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int, _dp, _dp] + [_dp] * 4 + [_dp]),
     'pem_loglik_marginal_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, _f8, _f8, _dp, _dp, _dp]),
+    'pem_loglik_marginal_scaled_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, _dp, _dp, _dp, _f8, _f8, _dp, C.c_int, _dp, _dp, _dp, C.c_int,
+                                                     _sz, _dp, C.c_int, _dp, _dp, _sz, _dp, _dp]),
     'pem_log_prior_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     'pem_jion_loglik_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int] + [_dp] * 6 + [_dp]),
     'pem_svd_compress_f64_dev': (C.c_int, [_sz, C.c_int, C.c_int, C.c_int, _f8, _dp, _dp, _dp, _dp]),

@@ -41,7 +41,7 @@ from .batch import CoupledBatch
 from .likelihood import JionLikelihood, SystemLikelihood
 from .models.coupled import COUPLED_INPUTS
 from .samplers import DRAM, DeviceDRAM, DeviceEnsemble, DeviceSMC, DeviceTemperedEnsemble, Metropolis, SMCResult  # noqa: F401
-from .sampling import LOGUNIFORM, NORMAL, PEM_V0_PRIORS, UNIFORM, Design
+from .sampling import LOGUNIFORM, NORMAL, PEM_V0_PRIORS, UNIFORM, Design, Prior
 
 Q_OVER_M = 1.6e-19 / 2.18e-25           # tests/sim_hallthruster.jl:36-37
 OPERATING = ('P_b', 'V_a', 'mdot_a')    # XE_ARRAY columns, mcmc.py:46
@@ -74,17 +74,84 @@ def log_prior(theta, names, priors=None):
     return total
 
 
+NOISE_PREFIX = 'noise_'
+NOISE_DISCHARGE = 'I_D'                 # the name of the discharge-current term among the noise scales
+NOISE_PRIOR = Prior(LOGUNIFORM, -1.0, 1.0, 'noise scale: s in [0.1, 10], density proportional to 1 / s')
+
+
+def noise_scale_table(noise_scales, qois, has_discharge, priors=None):
+    """The bookkeeping of `noise_scales` (DESIGN.md "Noise scales"), on the host: (scaled, merged) -- the scaled quantities in the
+    order given and a copy of `priors` that also holds their priors under 'noise_<name>'.  `noise_scales`: a sequence of names from
+    `qois` (and 'I_D' when the posterior has a discharge term of its own), or a dict {name: Prior}; the default prior is
+    `NOISE_PRIOR`.  ValueError for an unknown or repeated name, a NORMAL prior and a prior whose support reaches 0 or below."""
+    priors = PEM_V0_PRIORS if priors is None else priors
+    if isinstance(noise_scales, str):
+        noise_scales = (noise_scales,)
+    given = dict(noise_scales) if isinstance(noise_scales, dict) else {k: NOISE_PRIOR for k in noise_scales}
+    scaled = tuple(noise_scales)
+    offered = tuple(qois) + ((NOISE_DISCHARGE,) if has_discharge else ())
+    if not scaled:
+        raise ValueError(f'noise_scales names at least one of {offered} (None: no noise scale)')
+    merged = dict(priors)
+    for i, k in enumerate(scaled):
+        if k not in offered:
+            raise ValueError(f'noise_scales: unknown name {k!r}; this posterior offers {offered}')
+        if k in scaled[:i]:
+            raise ValueError(f'noise_scales: {k!r} is given twice')
+        p = given[k]
+        if not isinstance(p, Prior):
+            raise ValueError(f'noise_scales[{k!r}]: a sampling.Prior is needed, got {p!r}')
+        if p.kind == NORMAL:
+            raise ValueError(f'noise_scales[{k!r}]: a NORMAL prior puts mass on scales <= 0; use UNIFORM or LOGUNIFORM')
+        if p.kind not in (UNIFORM, LOGUNIFORM) or not (math.isfinite(p.a) and math.isfinite(p.b) and p.b > p.a):
+            raise ValueError(f'noise_scales[{k!r}]: a UNIFORM or LOGUNIFORM prior with finite a < b is needed, got {p!r}')
+        if p.kind == UNIFORM and not p.a > 0.0:
+            raise ValueError(f'noise_scales[{k!r}]: the support [{p.a}, {p.b}] reaches 0 or below; a scale is positive')
+        merged[NOISE_PREFIX + k] = p
+    return scaled, merged
+
+
+def noise_groups(lik):
+    """(qois, group_end int32, group_count float64) of a likelihood's table: one group of conditions per QoI in the order of
+    `SystemLikelihood.conditions`, each with its number of measured records (`span`; padding records are not counted).  A
+    `JionLikelihood` is one group."""
+    if not hasattr(lik, 'conditions'):
+        return ('jion',), np.asarray([lik.n_cond], dtype=np.int32), np.asarray([lik.n_cond * lik.n_ang], dtype=np.float64)
+    span = lik.span.cpu().numpy()
+    ends, counts, first = [], [], 0
+    for q in lik.qois:
+        sl = lik.conditions[q]
+        if sl.start != first or sl.stop <= sl.start:
+            raise ValueError(f'the conditions of {q!r} are {sl}: one contiguous ascending block per QoI is needed')
+        first = sl.stop
+        ends.append(sl.stop)
+        counts.append(float(span[sl, :, 1].sum()))
+    if first != lik.n_cond or len(ends) > _lib.NOISE_MAX_GROUPS:
+        raise ValueError(f'{len(ends)} groups ending at {first}: at most PEM_NOISE_MAX_GROUPS = {_lib.NOISE_MAX_GROUPS} groups '
+                         f'covering the {lik.n_cond} conditions')
+    return tuple(lik.qois), np.asarray(ends, dtype=np.int32), np.asarray(counts, dtype=np.float64)
+
+
 class BatchedPosterior:
     """What the posteriors of this module share: K chains x M nuisance draws x Ne operating conditions in one `CoupledBatch`,
-    the prior on the device, marginalisation, graph capture.  A subclass builds its likelihood and runs it (`_run_loglik`)."""
+    the prior on the device, marginalisation, graph capture.  A subclass builds its likelihood and runs it (`_run_loglik`).
+
+    noise_scales (None, names or {name: Prior}; `noise_scale_table`): one multiplicative scale of the stated std per named measured
+    quantity, sampled with theta.  `names` is then `model_names` followed by 'noise_<name>', `priors` holds their priors, every
+    method takes the (K, d_model + d_noise) table and the marginalisation is `pem_loglik_marginal_scaled_f64_dev` reading the
+    scales from theta itself.  None is the path without scales, launch for launch."""
 
     def _setup(self, theta_names, operating, make_likelihood, n_chains, n_nuisance, priors, seed, discharge, sweep_radius,
-               fresh_nuisance, shared_nuisance=False):
+               fresh_nuisance, shared_nuisance=False, noise_scales=None, qois=('jion',)):
         import torch
         if shared_nuisance and fresh_nuisance:
             raise ValueError('shared_nuisance needs fresh_nuisance=False: shared draws are the same on every evaluation')
-        self.names = tuple(theta_names)
-        for k in self.names:
+        self.model_names = tuple(theta_names)
+        self.noise = None
+        if noise_scales is not None:
+            self.noise, priors = noise_scale_table(noise_scales, qois, discharge is not None, priors)
+        self.names = self.model_names + tuple(NOISE_PREFIX + k for k in self.noise or ())
+        for k in self.model_names:
             if k not in COUPLED_INPUTS or k in OPERATING:
                 raise KeyError(f"'{k}' is not a calibratable input of the coupled model")
         op = np.atleast_2d(np.asarray(operating, dtype=np.float64))
@@ -101,7 +168,7 @@ class BatchedPosterior:
         self.device = self.batch.device
         self.design = Design(priors=self.priors, seed=seed)
         self.operating = torch.as_tensor(op, device=self.device)                       # (Ne, 3)
-        self.theta_rows = [COUPLED_INPUTS.index(k) for k in self.names]
+        self.theta_rows = [COUPLED_INPUTS.index(k) for k in self.model_names]
         self.op_rows = [COUPLED_INPUTS.index(k) for k in OPERATING]
         self.discharge = None if discharge is None else (float(discharge[0]), float(discharge[1]))
         self.fresh = bool(fresh_nuisance)
@@ -125,6 +192,12 @@ class BatchedPosterior:
         self._hi = np.ascontiguousarray([10.0 ** q.b if q.kind == LOGUNIFORM else q.b for q in pr], dtype=np.float64)
         self._lp = torch.empty(self.K, dtype=torch.float64, device=self.device)
         self._out = torch.empty(self.K, dtype=torch.float64, device=self.device)
+        if self.noise is not None:      # the groups of the scaled marginal: host arrays, passed by value with every launch
+            group_qois, self._group_end, self._group_count = noise_groups(self.lik)
+            col = {k: len(self.model_names) + j for j, k in enumerate(self.noise)}
+            self._scale_col = np.ascontiguousarray([col.get(q, -1) for q in group_qois], dtype=np.int32)
+            self._discharge_col = col.get(NOISE_DISCHARGE, -1)
+            self.noise_groups, self.noise_counts = group_qois, self._group_count      # the groups of chi and their record counts
 
     def _run_loglik(self):
         raise NotImplementedError
@@ -140,27 +213,48 @@ class BatchedPosterior:
             if self.fresh:
                 self.first_index += self.n
         x.index_copy_(0, self._op_idx, self._op_vals.expand(-1, self.K, self.M, -1))
+        if self.noise is not None:      # the model reads its own columns; the scales are the marginal's
+            theta = theta[:, :len(self.model_names)]
         x.index_copy_(0, self._theta_idx, theta.T[:, :, None, None].expand(-1, -1, self.M, self.Ne))
 
-    def _marginal(self, log_prior, out):
+    def _marginal(self, log_prior, out, theta=None, ess=None, chi=None):
         import torch
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None                                    # noqa: E731
         x = self.batch.inputs
         d = self.discharge
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pem_loglik_marginal_f64_dev(
-                self.K, self.M, self.Ne, p(self.loglik), p(x[COUPLED_INPUTS.index('mdot_a')]) if d else None,
-                p(x[COUPLED_INPUTS.index('a_1')]) if d else None, d[0] if d else 0.0, d[1] if d else 1.0, p(log_prior),
-                p(out), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            if self.noise is None:
+                _lib.check(_lib.load().pem_loglik_marginal_f64_dev(
+                    self.K, self.M, self.Ne, p(self.loglik), p(x[COUPLED_INPUTS.index('mdot_a')]) if d else None,
+                    p(x[COUPLED_INPUTS.index('a_1')]) if d else None, d[0] if d else 0.0, d[1] if d else 1.0, p(log_prior),
+                    p(out), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            else:                       # the scales are columns of theta itself: no gather, nothing extra in a captured graph
+                ptr = lambda arr: C.c_void_p(arr.ctypes.data)                                                # noqa: E731
+                _lib.check(_lib.load().pem_loglik_marginal_scaled_f64_dev(
+                    self.K, self.M, self.Ne, p(self.loglik), p(x[COUPLED_INPUTS.index('mdot_a')]) if d else None,
+                    p(x[COUPLED_INPUTS.index('a_1')]) if d else None, d[0] if d else 0.0, d[1] if d else 1.0, p(log_prior),
+                    len(self._group_end), ptr(self._group_end), ptr(self._group_count), p(theta), theta.shape[1], theta.stride(0),
+                    ptr(self._scale_col), self._discharge_col, p(ess), p(chi), chi.stride(0) if chi is not None else 0, p(out),
+                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return out
 
-    def log_likelihood(self, theta, out=None):
-        """theta: (K, n_theta) float64 tensor on the device -> (K,) marginal log-likelihoods."""
+    def log_likelihood(self, theta, out=None, diagnostics=False):
+        """theta: (K, n_theta) float64 tensor on the device -> (K,) marginal log-likelihoods.  diagnostics (with noise_scales):
+        (out, ess, chi) -- ess (K,) the effective number of nuisance draws behind each value, chi (K, n_groups + 1) the
+        likelihood-weighted unscaled sum of each group of `noise_groups` and of the discharge term (its last column)."""
         import torch
         assert theta.shape == (self.K, len(self.names)) and theta.dtype == torch.float64 and theta.device == self.device
+        if diagnostics and self.noise is None:
+            raise ValueError('diagnostics come from the scaled marginal: build the posterior with noise_scales')
+        theta = theta.contiguous() if self.noise is not None else theta
         self.assemble_inputs(theta)
         self._run_loglik()
-        return self._marginal(None, torch.empty_like(self._out) if out is None else out)
+        out = torch.empty_like(self._out) if out is None else out
+        if not diagnostics:
+            return self._marginal(None, out, theta)
+        ess = torch.empty_like(self._out)
+        chi = torch.empty((self.K, len(self._group_end) + 1), dtype=torch.float64, device=self.device)
+        return self._marginal(None, out, theta, ess, chi), ess, chi
 
     def log_prior(self, theta, out=None):
         """`log_prior(theta, names, priors)` of this module for a (K, n_theta) device tensor (`pem_log_prior_f64_dev`)."""
@@ -180,10 +274,11 @@ class BatchedPosterior:
         Five launches: nuisance draws, two row scatters, model + likelihood, marginalisation + prior."""
         import torch
         assert theta.shape == (self.K, len(self.names)) and theta.dtype == torch.float64 and theta.device == self.device
+        theta = theta.contiguous() if self.noise is not None else theta
         self.log_prior(theta, out=self._lp)
         self.assemble_inputs(theta)
         self._run_loglik()
-        return self._marginal(self._lp, torch.empty_like(self._out) if out is None else out)
+        return self._marginal(self._lp, torch.empty_like(self._out) if out is None else out, theta)
 
     # ---------------------------------------------------------------------------------------------- graph capture
     def capture(self):
@@ -208,7 +303,7 @@ class BatchedPosterior:
 class JionPosterior(BatchedPosterior):
     def __init__(self, theta_names, operating, alpha, y, std, n_chains: int, n_nuisance: int = 100, priors=None,
                  seed: int = 0, discharge=(4.5, 0.2), sweep_radius: float = 1.0, fresh_nuisance: bool = True,
-                 device=None, shared_nuisance: bool = False):
+                 device=None, shared_nuisance: bool = False, noise_scales=None):
         """theta_names: calibrated inputs (subset of the 15 coupled inputs, not operating ones);
         operating: (Ne, 3) array of `P_b [Torr], V_a [V], mdot_a [kg/s]` per experiment;
         alpha, y, std: (Ne, Na) measurement angles [rad], current densities and standard deviations at `sweep_radius`;
@@ -217,9 +312,10 @@ class JionPosterior(BatchedPosterior):
         draws are whatever was recorded (common random numbers);
         shared_nuisance: every row uses draws 0 .. M Ne - 1 of the design, so that a value depends on theta, seed, M and the
         data and not on the row or on K (what an optimizer or a finite-difference Hessian comparing rows needs); requires
-        fresh_nuisance=False.  Otherwise row k uses draws k M Ne .. (k + 1) M Ne - 1."""
+        fresh_nuisance=False.  Otherwise row k uses draws k M Ne .. (k + 1) M Ne - 1;
+        noise_scales: None, ('jion',), ('jion', 'I_D') or {name: Prior} (`BatchedPosterior`): all measurements are one group."""
         self._setup(theta_names, operating, lambda: JionLikelihood(alpha, y, std, device=device), n_chains, n_nuisance, priors,
-                    seed, discharge, sweep_radius, fresh_nuisance, shared_nuisance)
+                    seed, discharge, sweep_radius, fresh_nuisance, shared_nuisance, noise_scales, ('jion',))
 
     def _run_loglik(self):
         self.batch.run_loglik(self.lik, out=self.loglik)
@@ -227,17 +323,19 @@ class JionPosterior(BatchedPosterior):
 
 class SystemPosterior(BatchedPosterior):
     def __init__(self, theta_names, likelihood: SystemLikelihood, n_chains: int, n_nuisance: int = 100, priors=None,
-                 seed: int = 0, discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False):
+                 seed: int = 0, discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False, noise_scales=None):
         """The posterior of the reference's `System` calibration (mcmc.py:28-130): V_cc, thrust, ion velocity and ion current
         density, each from its own dataset (`likelihood.SystemLikelihood`, whose conditions are the Ne operating conditions
         here), evaluated by ONE fused launch (`pem_coupled_system_loglik_f64_dev`) per evaluation.  The interface of
         `JionPosterior`; theta_names, n_chains, n_nuisance, priors, seed, fresh_nuisance, shared_nuisance as there.
         discharge: (I_d, sigma) of the discharge-current weight added for every condition, or None; dropped when the
-        likelihood's component is 'Cathode' (mcmc.py:100-101)."""
+        likelihood's component is 'Cathode' (mcmc.py:100-101).
+        noise_scales: None, names from `likelihood.qois` (and 'I_D' while there is a discharge term) or {name: Prior}
+        (`BatchedPosterior`): one group of conditions per QoI."""
         if not likelihood.use_discharge:
             discharge = None
         self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, priors, seed, discharge,
-                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance)
+                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance, noise_scales, likelihood.qois)
 
     def _run_loglik(self):
         self.batch.run_system_loglik(self.lik, out=self.loglik)
@@ -311,7 +409,7 @@ def surrogate_input_map(theta_names, operating, varied, fixed, priors, qois=(), 
 
 class SurrogatePosterior(BatchedPosterior):
     def __init__(self, theta_names, likelihood: SystemLikelihood, surrogate, n_chains: int, n_nuisance: int = 100, seed: int = 0,
-                 discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False):
+                 discharge=(4.5, 0.2), fresh_nuisance: bool = True, shared_nuisance: bool = False, noise_scales=None):
         """`SystemPosterior` with a trained `chain.ChainedSurrogate` in the model's place, as the reference calibrates
         (mcmc.py:57-106: `SURR.predict`, `jion_reconstruct`, I_D from the surrogate's output).  The interface of
         `SystemPosterior`.  The priors are the surrogate's (its coordinates are defined over them); inputs it holds fixed are
@@ -321,13 +419,18 @@ class SurrogatePosterior(BatchedPosterior):
         surrogate's I_B0), then `pem_loglik_marginal_f64_dev` without a discharge term of its own.  `likelihood` may hold V_cc, T
         and jion records, and uion records when the surrogate was built with `u_ion` (the launch is then
         `pem_chain_fields_loglik_f64_dev`: all four quantities of `QOI_MAP['System']`); otherwise uion is refused
-        (`surrogate_input_map`)."""
+        (`surrogate_input_map`).
+        noise_scales: as `SystemPosterior`'s, with discharge=None only: this launch adds the discharge term into the per-sample
+        sums, which are then not separable by quantity; 'I_D' is not offered."""
         import torch
         if len(likelihood.sweep_radii) > 1:
             raise ValueError(f'the likelihood holds j_ion at several sweep radii {likelihood.sweep_radii}: the plume surrogate is '
                              f'trained at one radius')
         if not likelihood.use_discharge:
             discharge = None
+        if noise_scales is not None and discharge is not None:
+            raise ValueError('noise_scales needs discharge=None here: the chained launch adds the discharge term into the per-sample '
+                             'sums, so they cannot be scaled per quantity afterwards')
         self.surrogate = surrogate
         self.map = surrogate_input_map(theta_names, likelihood.operating, surrogate.varied, surrogate.fixed, surrogate.priors,
                                        likelihood.qois, field=surrogate.field is not None,
@@ -335,7 +438,7 @@ class SurrogatePosterior(BatchedPosterior):
         if likelihood.device != surrogate.device:
             raise ValueError(f'the likelihood lives on {likelihood.device}, the surrogate on {surrogate.device}')
         self._setup(theta_names, likelihood.operating, lambda: likelihood, n_chains, n_nuisance, surrogate.priors, seed, None,
-                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance)
+                    likelihood.sweep_radius, fresh_nuisance, shared_nuisance, noise_scales, likelihood.qois)
         self.chain_discharge = None if discharge is None else (float(discharge[0]), float(discharge[1]))   # added by the launch
         dev = lambda a, **kw: torch.as_tensor(a, device=self.device, **kw)                                   # noqa: E731
         m = self.map

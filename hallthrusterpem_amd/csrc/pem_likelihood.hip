@@ -179,6 +179,177 @@ __global__ __launch_bounds__(BLOCK) void loglik_marginal_kernel(int n_draws, int
     }
 }
 
+// ---- the same marginal with one noise scale per group of conditions (DESIGN.md "Noise scales") ----------------------------
+// s_g multiplies the stated std of every record of group g, so its per-sample sums count w_g = 1 / s_g^2 times and the density
+// gains the normaliser -n_g log s_g.  The draws go to the lanes and through the push / merge tree exactly as above, and a weight
+// of 1.0 leaves every sum as it was (fma(x, 1.0, s) rounds as s + x): at scale 1 the result is loglik_marginal_kernel's, bit for
+// bit.  DIAG carries sum p^2 and sum p C_g (p = exp(S - max), C_g the unscaled sum of group g, the discharge sum last) through
+// the same state, rescaled with acc: the effective number of draws and d L / d w_g without a second pass over ll.
+constexpr int NG = PEM_NOISE_MAX_GROUPS;
+
+struct NoiseGroups {              // by value in the kernel arguments; entries past n_groups: end = n_cond, col = -1, count = 0
+    int end[NG], col[NG];
+    double count[NG];
+    int n_groups, discharge_col;
+};
+
+template <bool DIAG>
+struct LseW {
+    double mx, acc;
+};
+template <>
+struct LseW<true> {
+    double mx, acc, acc2, cw[NG + 1];
+};
+
+template <bool DIAG>
+__device__ __forceinline__ LseW<DIAG> lsew_push(LseW<DIAG> a, double s, const double (&c)[NG + 1]) {
+    if (s > a.mx) {
+        const double e = exp(a.mx - s);
+        const bool empty = a.acc == 0.0;
+        a.acc = (a.acc == 0.0 ? 0.0 : a.acc * e) + 1.0;
+        if constexpr (DIAG) {
+            a.acc2 = (empty ? 0.0 : a.acc2 * e * e) + 1.0;
+#pragma unroll
+            for (int g = 0; g <= NG; ++g) a.cw[g] = (empty ? 0.0 : a.cw[g] * e) + c[g];
+        }
+        a.mx = s;
+    } else if (s != -__builtin_inf()) {
+        const double p = exp(s - a.mx);   // NaN s lands here and poisons every sum
+        a.acc += p;
+        if constexpr (DIAG) {
+            a.acc2 = fma(p, p, a.acc2);
+#pragma unroll
+            for (int g = 0; g <= NG; ++g) a.cw[g] = fma(p, c[g], a.cw[g]);
+        }
+    }
+    return a;
+}
+
+template <bool DIAG>
+__device__ __forceinline__ LseW<DIAG> lsew_merge(LseW<DIAG> a, const LseW<DIAG>& b) {
+    const double m = fmax(a.mx, b.mx);
+    const double ea = exp(a.mx - m), eb = exp(b.mx - m);
+    const bool za = a.acc == 0.0, zb = b.acc == 0.0;
+    const double ta = a.acc == 0.0 ? 0.0 : a.acc * ea;
+    const double tb = b.acc == 0.0 ? 0.0 : b.acc * eb;
+    if constexpr (DIAG) {
+        a.acc2 = (za ? 0.0 : a.acc2 * ea * ea) + (zb ? 0.0 : b.acc2 * eb * eb);
+#pragma unroll
+        for (int g = 0; g <= NG; ++g) a.cw[g] = (za ? 0.0 : a.cw[g] * ea) + (zb ? 0.0 : b.cw[g] * eb);
+    }
+    a.mx = m;
+    a.acc = ta + tb;
+    return a;
+}
+
+template <bool DIAG>
+__device__ __forceinline__ LseW<DIAG> lsew_shfl(const LseW<DIAG>& a, int sh) {
+    LseW<DIAG> b;
+    b.mx = __shfl_xor(a.mx, sh);
+    b.acc = __shfl_xor(a.acc, sh);
+    if constexpr (DIAG) {
+        b.acc2 = __shfl_xor(a.acc2, sh);
+#pragma unroll
+        for (int g = 0; g <= NG; ++g) b.cw[g] = __shfl_xor(a.cw[g], sh);
+    }
+    return b;
+}
+
+template <bool DIAG>
+__global__ __launch_bounds__(BLOCK) void loglik_marginal_scaled_kernel(
+    int n_draws, int n_cond, const double* __restrict__ ll, const double* __restrict__ mdot_a, const double* __restrict__ a_1,
+    double discharge, double inv_sigma, const double* __restrict__ log_prior, NoiseGroups grp, const double* __restrict__ theta,
+    long long ld_theta, double* __restrict__ ess, double* __restrict__ chi, long long ld_chi, double* __restrict__ out) {
+    __shared__ LseW<DIAG> part[WAVES];
+    __shared__ double wgt[NG + 1], lgs[NG + 1];       // the row's weights 1 / s^2 and log s; entry NG: the discharge term
+    // lane g of the first wave owns group g: one reciprocal, one square and one log per row, not per thread
+    if (threadIdx.x <= NG) {
+        const int g = threadIdx.x;
+        int col = grp.discharge_col;
+#pragma unroll
+        for (int j = 0; j < NG; ++j) col = g == j ? grp.col[j] : col;
+        double w = 1.0, l = 0.0;
+        if (col >= 0) {
+            const double s = theta[(long long)blockIdx.x * ld_theta + col];
+            const bool ok = s > 0.0 && s < __builtin_inf();
+            const double inv = 1.0 / s;
+            w = ok ? inv * inv : __builtin_nan("");
+            l = ok ? log(s) : __builtin_nan("");
+        }
+        wgt[g] = w;
+        lgs[g] = l;
+    }
+    __syncthreads();
+    double w[NG + 1];
+#pragma unroll
+    for (int g = 0; g <= NG; ++g) w[g] = wgt[g];
+
+    const long long base = (long long)blockIdx.x * n_draws * n_cond;
+    LseW<DIAG> st;
+    st.mx = -__builtin_inf();
+    st.acc = 0.0;
+    if constexpr (DIAG) {
+        st.acc2 = 0.0;
+#pragma unroll
+        for (int g = 0; g <= NG; ++g) st.cw[g] = 0.0;
+    }
+    for (int m = threadIdx.x; m < n_draws; m += BLOCK) {
+        const long long row = base + (long long)m * n_cond;
+        double s = 0.0, c[NG + 1];
+        int e = 0;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {                // groups are contiguous and ascending: e runs 0 .. n_cond - 1 in order
+            double cg = 0.0;
+            for (; e < grp.end[g]; ++e) {
+                const double v = ll[row + e];
+                s = fma(v, w[g], s);
+                if constexpr (DIAG) cg += v;
+            }
+            c[g] = cg;
+        }
+        c[NG] = 0.0;
+        if (mdot_a) {
+            double t = 0.0;
+            for (int e2 = 0; e2 < n_cond; ++e2) {
+                const double i_d = (1.6e-19 / 2.18e-25) * mdot_a[row + e2] / (1.0 - a_1[row + e2] * 2.0);
+                const double z = (discharge - i_d) * inv_sigma;
+                t = fma(-0.5 * z, z, t);
+            }
+            s = fma(t, w[NG], s);
+            c[NG] = t;
+        }
+        st = lsew_push<DIAG>(st, s, c);
+    }
+    for (int sh = 32; sh >= 1; sh >>= 1) st = lsew_merge<DIAG>(st, lsew_shfl<DIAG>(st, sh));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = st;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int wv = 1; wv < WAVES; ++wv) st = lsew_merge<DIAG>(st, part[wv]);
+        double cn = 0.0;                              // the normaliser sum_g n_g log s_g (+ n_cond log s_d), in group order
+#pragma unroll
+        for (int g = 0; g < NG; ++g) cn = fma(grp.count[g], lgs[g], cn);
+        if (grp.discharge_col >= 0) cn = fma((double)n_cond, lgs[NG], cn);
+        double r = st.mx + log(st.acc) - cn;          // all -inf: -inf + log(0) = -inf
+        if (st.acc != st.acc) r = st.acc;             // NaN
+        if (log_prior) {
+            const double lp = log_prior[blockIdx.x];
+            r = (lp - lp == 0.0 && r == r) ? lp + r : -__builtin_inf();
+        }
+        out[blockIdx.x] = r;
+        if constexpr (DIAG) {
+            if (ess) ess[blockIdx.x] = st.acc * st.acc / st.acc2;
+            if (chi) {
+                double* crow = chi + (long long)blockIdx.x * ld_chi;
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+                    if (g < grp.n_groups) crow[g] = st.cw[g] / st.acc;
+                crow[grp.n_groups] = st.cw[NG] / st.acc;
+            }
+        }
+    }
+}
+
 // lo / hi: the support of a log-uniform entry, [10^a, 10^b] as the caller rounded it.  The device's pow(10, a) is not the host's
 // 10.0 ** a (the P_b prior's edges differ by an ulp), and the support decision has to be calibration.log_prior's bit for bit.
 struct PriorTable {
@@ -222,6 +393,60 @@ extern "C" int pem_loglik_marginal_f64_dev(size_t n_chains, int n_draws, int n_c
     hipLaunchKernelGGL(loglik_marginal_kernel, dim3((unsigned)n_chains), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
                        n_draws, n_cond, loglik, mdot_a, a_1, discharge_current, mdot_a ? 1.0 / discharge_sigma : 0.0, log_prior,
                        out);
+    HIP_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
+extern "C" int pem_loglik_marginal_scaled_f64_dev(size_t n_chains, int n_draws, int n_cond, const double* loglik, const double* mdot_a,
+                                                  const double* a_1, double discharge_current, double discharge_sigma,
+                                                  const double* log_prior, int n_groups, const int* group_end,
+                                                  const double* group_count, const double* theta, int d, size_t ld_theta,
+                                                  const int* scale_col, int discharge_col, double* ess, double* chi, size_t ld_chi,
+                                                  double* out, pem_stream_t stream) {
+    if (n_draws < 1 || n_cond < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: need n_draws, n_cond >= 1");
+    if (n_groups < 1 || n_groups > PEM_NOISE_MAX_GROUPS)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: n_groups %d outside [1, PEM_NOISE_MAX_GROUPS = %d]", n_groups,
+                         PEM_NOISE_MAX_GROUPS);
+    if (!group_end || !group_count || !scale_col) return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: NULL group table");
+    if (theta && (d < 1 || ld_theta < (size_t)d))
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: theta needs d >= 1 and ld_theta >= d, got d %d ld_theta %zu", d, ld_theta);
+    const int n_col = theta ? d : 0;                  // without a table every column has to be -1
+    NoiseGroups grp;
+    for (int g = 0; g < NG; ++g) grp.end[g] = n_cond, grp.col[g] = -1, grp.count[g] = 0.0;
+    for (int g = 0, prev = 0; g < n_groups; prev = group_end[g++]) {
+        if (group_end[g] <= prev || group_end[g] > n_cond)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: group_end[%d] = %d: the ends must ascend strictly within (0, n_cond = %d]",
+                             g, group_end[g], n_cond);
+        if (!(group_count[g] >= 0.0) || group_count[g] - group_count[g] != 0.0)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: group_count[%d] = %g: a finite count >= 0 is needed", g, group_count[g]);
+        if (scale_col[g] < -1 || scale_col[g] >= n_col)
+            return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: scale_col[%d] = %d outside [-1, d = %d)", g, scale_col[g], n_col);
+        grp.end[g] = group_end[g], grp.col[g] = scale_col[g], grp.count[g] = group_count[g];
+    }
+    if (group_end[n_groups - 1] != n_cond)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: the last group ends at %d, not at n_cond = %d", group_end[n_groups - 1], n_cond);
+    if (discharge_col < -1 || discharge_col >= n_col)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: discharge_col = %d outside [-1, d = %d)", discharge_col, n_col);
+    if (discharge_col >= 0 && !mdot_a)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: discharge_col given without a discharge term (mdot_a is NULL)");
+    if (chi && ld_chi < (size_t)n_groups + 1)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: ld_chi %zu < n_groups + 1 = %d", ld_chi, n_groups + 1);
+    if (ld_theta > 0x7fffffffffffffffull / 2 || ld_chi > 0x7fffffffffffffffull / 2)
+        return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: leading dimension too large");
+    grp.n_groups = n_groups, grp.discharge_col = discharge_col;
+    if (n_chains == 0) return PEM_OK;
+    if (!loglik || !out || (mdot_a && !a_1)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: NULL array");
+    if (mdot_a && !(discharge_sigma > 0.0)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: discharge_sigma must be > 0");
+    if (n_chains > 0x7fffffffull) return pem::fail(PEM_ERR_INVALID_ARG, "pem_loglik_marginal_scaled: too many chains");
+    if (int rc = pem::check_device()) return rc;
+    const double inv_sigma = mdot_a ? 1.0 / discharge_sigma : 0.0;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ess || chi)
+        hipLaunchKernelGGL(loglik_marginal_scaled_kernel<true>, dim3((unsigned)n_chains), dim3(BLOCK), 0, s, n_draws, n_cond, loglik, mdot_a,
+                           a_1, discharge_current, inv_sigma, log_prior, grp, theta, (long long)ld_theta, ess, chi, (long long)ld_chi, out);
+    else
+        hipLaunchKernelGGL(loglik_marginal_scaled_kernel<false>, dim3((unsigned)n_chains), dim3(BLOCK), 0, s, n_draws, n_cond, loglik, mdot_a,
+                           a_1, discharge_current, inv_sigma, log_prior, grp, theta, (long long)ld_theta, ess, chi, (long long)ld_chi, out);
     HIP_TRY(hipGetLastError());
     return PEM_OK;
 }

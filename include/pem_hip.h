@@ -355,6 +355,29 @@ int pem_coupled_latent_f64_dev(size_t n, double torr2pa, double radius, const do
 int pem_loglik_marginal_f64_dev(size_t n_chains, int n_draws, int n_cond, const double* loglik, const double* mdot_a,
                                 const double* a_1, double discharge_current, double discharge_sigma,
                                 const double* log_prior, double* out, pem_stream_t stream);
+/* The same marginal with one multiplicative noise scale per group of conditions, read from the calibration table itself
+ * (DESIGN.md "Noise scales").  Group g is conditions group_end[g-1] .. group_end[g] - 1 and holds group_count[g] measured records;
+ * its scale on chain k is s_g = theta[k * ld_theta + scale_col[g]], or 1 exactly where scale_col[g] is -1; discharge_col is the
+ * same for the discharge term (-1: discharge_sigma as given).  With w = (1 / s)^2:
+ *     S[k][m] = sum_e loglik[k][m][e] * w_g(e) + w_d * sum_e -0.5 ((discharge_current - I_d[k][m][e]) / discharge_sigma)^2
+ *     out[k]  = logsumexp_m S[k][m] - sum_g group_count[g] log s_g - n_cond log s_d          (+ log_prior as above)
+ * A scale that is not finite and > 0 makes the likelihood NaN (-inf with log_prior).  With every scale 1 (or every column -1) out
+ * is pem_loglik_marginal_f64_dev's bit for bit.  ess (NULL or [n_chains]): (sum_m p_m)^2 / sum_m p_m^2, p_m = exp(S_m - max), the
+ * effective number of nuisance draws behind out.  chi (NULL or [n_chains][ld_chi], ld_chi >= n_groups + 1): sum_m p_m C_mg / sum_m
+ * p_m, C_mg the UNSCALED sum of group g's conditions, in the last column that of the discharge term (0 without one): d out / d w_g
+ * at fixed normaliser.  Both are NaN where the likelihood is not finite.  One workgroup per chain, no atomics: the same bits on
+ * every run.  group_end, group_count, scale_col: HOST arrays [n_groups], read before return.  theta: DEVICE [n_chains][ld_theta]
+ * with d columns, or NULL when every column is -1.
+ * Refused with PEM_ERR_INVALID_ARG before any device call: n_groups outside [1, PEM_NOISE_MAX_GROUPS]; group_end not strictly
+ * ascending within (0, n_cond] or not ending at n_cond; a negative or non-finite count; a column outside [-1, d); d < 1 or
+ * ld_theta < d; discharge_col >= 0 with mdot_a NULL; ld_chi < n_groups + 1; a NULL group table; what pem_loglik_marginal_f64_dev
+ * refuses.                                                                                                            */
+#define PEM_NOISE_MAX_GROUPS 8
+int pem_loglik_marginal_scaled_f64_dev(size_t n_chains, int n_draws, int n_cond, const double* loglik, const double* mdot_a,
+                                       const double* a_1, double discharge_current, double discharge_sigma,
+                                       const double* log_prior, int n_groups, const int* group_end, const double* group_count,
+                                       const double* theta, int d, size_t ld_theta, const int* scale_col, int discharge_col,
+                                       double* ess, double* chi, size_t ld_chi, double* out, pem_stream_t stream);
 /* out[i] = sum_d log pdf_d(theta[i][d]) for the PEM_DIST_* table (kind, a, b: host arrays, ndim <= 32); -inf outside
  * the support of a uniform / log-uniform variable.  lo, hi (host arrays or NULL): the support [lo, hi] of each log-uniform
  * entry, ignored for the other kinds.  A caller that also decides the support itself passes the 10^a, 10^b it compares
