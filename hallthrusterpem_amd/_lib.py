@@ -105,7 +105,6 @@ SIGNATURES = {
                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.c_int, C.c_int, _dp, _dp,
                                                   _dp, _f8, _f8, _dp, _dp, _sz, _dp, _sz,
                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, C.c_int, _dp, _dp, _dp]),
-    'pem_key_minmax_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, _dp, _dp, _dp, _dp]),
     'pem_range_hist_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _sz, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     'pem_range_narrow_dev': (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     'pem_qsel_bins': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

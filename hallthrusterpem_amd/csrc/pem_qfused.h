@@ -24,7 +24,7 @@ struct Bracket {         // per (column, quantile): the keys lo .. hi, binned on
 };
 
 struct Record {          // a profile value inside a bracket
-    unsigned long long key;     // its order-preserving image (pem_quantile.hip key_of)
+    unsigned long long key;     // its order-preserving image (pem_quantile_core.h key_of)
     unsigned long long col;     // its column (which of the column's brackets holds the key: their high words say)
 };
 
@@ -72,7 +72,8 @@ __attribute__((visibility("hidden"))) int launch_coupled_mc(const McLaunch& a, h
 __attribute__((visibility("hidden"))) int coupled_count_waves(size_t n, int nq, bool store_profile, unsigned* waves);
 __attribute__((visibility("hidden"))) int launch_coupled_mc_count(const McLaunch& a, const CountIO& c, bool store_profile, hipStream_t st);
 
-// csrc/pem_quantile.hip: the selection driven by a producer of counts and records instead of by passes over an array
+// csrc/pem_quantile.hip: the selection driven by a producer of counts and records instead of by passes over an array (the passes
+// over the records: csrc/pem_quantile_records.h)
 struct FusedProducer {
     virtual ~FusedProducer() {}
     // the premask (see CountIO): which two of the quantiles are the quartiles, the IQR factor, where the per-sample counts go;

@@ -19,10 +19,14 @@
 // 1e-20 profile of invalid samples -- is narrowed by further histograms over the list itself until it fits or is one value.
 // Monotone binning is all the method needs: a bin index that never decreases with the key, so that everything in a lower
 // bin is <= everything in a higher one and equal keys share a bin.
+// The keys, their binning, a lane's columns, the streaming loop and the selection from a list are in csrc/pem_quantile_core.h,
+// the record passes of the fused form in csrc/pem_quantile_records.h; the selection over samples sharded over ranks has units of
+// its own (csrc/pem_quantile_sharded.hip, and the level loop it falls back to: csrc/pem_quantile_range.hip).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
@@ -30,145 +34,9 @@
 #include "pem_common.h"
 #include "pem_hip.h"
 #include "pem_qfused.h"
+#include "pem_quantile_core.h"
 
 namespace {
-
-typedef unsigned long long u64;
-constexpr int QBLOCK = 512;               // two waves per SIMD share one workgroup's LDS histogram
-constexpr int QWAVES = QBLOCK / 64;
-constexpr int LDS_WORDS = 36864;          // 144 KB of 32-bit counters per workgroup
-constexpr int SORT_CAP = 4096;            // keys a workgroup's LDS sort buffer holds (32 KB)
-constexpr int SORT_DIRECT = 512;          // ... and sorts without narrowing the list first: a bitonic sort of 4096 keys is 78 passes with a
-                                          // barrier each (80 us for the 910 lists of a campaign), one 1024-bin narrowing round three
-constexpr int MAX_NC = 4;                 // columns per lane: m <= 256
-constexpr int UNROLL = 8;                 // row groups a wave requests before it consumes any (loads in flight per lane: UNROLL x NC)
-static_assert(PEM_QUANTILE_MAX_Q == 6, "hist2_kernel / compact_kernel are instantiated for 2, 4, ... 12 ranks per column");
-
-// order-preserving image of a double (NaN excluded by the callers): negative values reversed, sign bit flipped
-__device__ __forceinline__ u64 key_of(double x) {
-    const u64 b = (u64)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double value_of(u64 k) {
-    const u64 b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-// Binning of the streaming passes, in integer arithmetic (a u64 -> f64 conversion is six instructions on this chip, and the
-// passes over 7 GB were bound by them): d = (k - lo) >> shift fits 31 bits, bin = floor(d * mult / 2^32) with
-// mult = floor(2^32 BINS / (D + 1)), D = (hi - lo) >> shift -- never decreases with the key and stays below BINS; the low
-// 32 bits of the product are the position inside the bin, scaled to BINS2 sub-bins the same way.
-struct Scale {
-    u64 lo;
-    unsigned mult;
-    int shift;
-};
-__device__ __forceinline__ int bin_of(u64 k, const Scale& s, unsigned& frac) {
-    const unsigned d = (unsigned)((k - s.lo) >> s.shift);
-    const u64 p = (u64)d * s.mult;
-    frac = (unsigned)p;
-    return (int)(p >> 32);
-}
-__device__ __forceinline__ int subbin_of(unsigned frac, int bins2) { return (int)__umulhi(frac, (unsigned)bins2); }
-// The keys of bin b (bins2 = 1, g = b) or of sub-bin (b, sb) (g = b bins2 + sb) of a column's binning, [klo, khi], by bisection on
-// the monotone map d -> bin(d) bins2 + sub-bin(d).  The streaming passes test a value's HIGH word against these ranges (two 32-bit
-// instructions per wanted bin) before they bin it in full: a value outside every wanted bin -- all but a few per cent -- costs
-// neither the 64-bit subtraction nor the quarter-rate multiply of bin_of.  An empty bin comes out as klo > khi.
-__device__ __forceinline__ void keys_of_bin(const Scale& sc, u64 kmax, int bins2, long long g, u64& klo, u64& khi) {
-    const u64 D = kmax >= sc.lo ? (kmax - sc.lo) >> sc.shift : 0;
-    auto first = [&](long long G) {
-        u64 lo = 0, hi = D + 1;
-        while (lo < hi) {
-            const u64 mid = (lo + hi) >> 1, prod = mid * sc.mult;
-            const long long gd = (long long)(prod >> 32) * bins2 + (bins2 > 1 ? (long long)__umulhi((unsigned)prod, (unsigned)bins2) : 0);
-            if (gd >= G) hi = mid;
-            else lo = mid + 1;
-        }
-        return lo;
-    };
-    const u64 d0 = first(g), d1 = first(g + 1);
-    klo = sc.lo + (d0 << sc.shift);
-    khi = d1 > D ? kmax : sc.lo + (d1 << sc.shift) - 1;
-    if (d0 > D || d0 >= d1) {
-        klo = ~0ull;
-        khi = 0ull;
-    }
-}
-// the select kernel's own refinement (rare, over short lists): bins in double arithmetic over any key range
-__device__ __forceinline__ int bin_of_d(u64 k, u64 lo, double inv, int bins) {
-    const int b = (int)((double)(k - lo) * inv);
-    return b < bins - 1 ? b : bins - 1;
-}
-
-struct Column {          // per column
-    u64 kmin, kmax;
-    int has_nan, pad;    // has_nan: the number of NaNs the min / max pass met (the pilot form's counting pass only flags: 1)
-    unsigned mult;       // floor(2^32 BINS1 / (((kmax - kmin) >> shift) + 1))
-    int shift;           // so that (kmax - kmin) >> shift < 2^31
-};
-struct Target {          // per (column, wanted rank)
-    u64 rank;            // in: 0-based rank in the column; then the rank inside the current bin / list
-    u64 count;           // values in the target's sub-bin (= length of its list)
-    u64 offset;          // start of its list in the candidate buffer
-    u64 cursor;          // append position during pass 4
-    u64 answer;          // the key x_(rank)
-    int bin1, bin2;
-    int owner;           // index of the target (of this column) whose list this one shares, or its own index
-    int done;            // answer already known (constant column)
-};
-
-// lane -> the columns it owns.  m <= 64: a wave instruction covers rpw = 64 / m whole rows (lane = row-in-group * m + column);
-// m > 64: one row per wave instruction and chunk, column = lane + 64 chunk.
-struct Lanes {
-    int rpw, active, col0, rsub;
-    size_t cs = 1;       // elements between consecutive columns of a row (1: row-major [n][ld]; n with ld = 1: the transposed [m][n])
-    __device__ Lanes(int m, int lane, size_t col_stride = 1) : cs(col_stride) {
-        if (m <= 64) {
-            rpw = 64 / m;
-            active = lane < rpw * m;
-            col0 = lane % m;
-            rsub = lane / m;
-        } else {
-            rpw = 1;
-            active = 1;
-            col0 = lane;
-            rsub = 0;
-        }
-    }
-};
-
-// Every value of the array once: f(j, column, x) for the lane's j-th column.  A wave takes UNROLL consecutive row groups at a
-// time and requests all their values before it consumes the first (with one workgroup of 144 KB of LDS per CU the memory
-// latency has to be covered inside the wave).
-template <int NC, int U = UNROLL, class F>
-__device__ __forceinline__ void stream_values(long long n, int m, size_t ld, const double* __restrict__ data, const Lanes& L, F f) {
-    const long long wave = (long long)blockIdx.x * QWAVES + (threadIdx.x >> 6), nwaves = (long long)gridDim.x * QWAVES;
-    const long long groups = (n + L.rpw - 1) / L.rpw;
-    for (long long g0 = wave * U; g0 < groups; g0 += nwaves * U) {
-        double x[U][NC];
-        bool ok[U][NC];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long long row = (g0 + u) * L.rpw + L.rsub;
-#pragma unroll
-            for (int j = 0; j < NC; ++j) {
-                const int c = L.col0 + 64 * j;
-                ok[u][j] = L.active && c < m && row < n;
-                x[u][j] = ok[u][j] ? data[(size_t)row * ld + (size_t)c * L.cs] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int j = 0; j < NC; ++j)
-                if (ok[u][j]) f(j, L.col0 + 64 * j, x[u][j]);
-        }
-    }
-}
-
-struct Wanted {          // the call's quantiles travel in the kernel arguments (nq <= 3): no host-to-device copy to wait for
-    u64 prev[PEM_QUANTILE_MAX_Q], next[PEM_QUANTILE_MAX_Q];
-    double gamma[PEM_QUANTILE_MAX_Q];
-};
 
 __global__ void init_columns_kernel(Column* col, Target* tg, int m, int nq, Wanted w) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -278,46 +146,6 @@ __global__ __launch_bounds__(QBLOCK) void hist1_kernel(long long n, int m, size_
         const unsigned v = lds_hist[i];
         if (v) atomicAdd(&hist1[i], v);
     }
-}
-
-// The bin of a histogram that holds `rank` (0-based among the counted values), searched by one WAVE: every lane sums a
-// chunk of the bins, the lanes' sums are scanned with shuffles, the lane whose chunk holds the rank walks it.  (One thread
-// walking 4096 bins in global memory took 0.4-0.9 ms per launch -- more than the four passes over a scalar QoI's data.)
-struct Found {
-    int bin;
-    u64 before;      // values in the bins below
-    unsigned count;  // values in the bin
-};
-__device__ __forceinline__ Found find_bin(const unsigned* __restrict__ h, int bins, u64 rank, int lane) {
-    const int per = (bins + 63) / 64, b0 = lane * per;
-    u64 mine = 0;
-    for (int b = b0; b < b0 + per && b < bins; ++b) mine += h[b];
-    u64 incl = mine;
-#pragma unroll
-    for (int sh = 1; sh < 64; sh <<= 1) {
-        const u64 up = __shfl_up(incl, sh);
-        if (lane >= sh) incl += up;
-    }
-    const unsigned long long holds = __ballot(incl > rank);
-    const int src = holds ? __builtin_ctzll(holds) : 63;
-    u64 cum = __shfl(incl - mine, src);
-    const int s0 = src * per;
-    int bin = s0;
-    unsigned cnt = 0;
-    if (lane == src) {
-        int last = s0 + per < bins ? s0 + per : bins;
-        for (; bin < last - 1; ++bin) {
-            if (cum + h[bin] > rank) break;
-            cum += h[bin];
-        }
-        if (bin > bins - 1) bin = bins - 1;
-        cnt = h[bin];
-    }
-    Found f;
-    f.bin = __shfl(bin, src);
-    f.before = __shfl(cum, src);
-    f.count = (unsigned)__shfl((int)cnt, src);
-    return f;
 }
 
 // one wave per (column, target): the bin that holds the rank
@@ -514,147 +342,6 @@ __global__ __launch_bounds__(QBLOCK) void compact_kernel(long long n, int m, siz
     });
 }
 
-// ---- the lists: one workgroup per (column, target) ----------------------------------------------------------------------------
-__device__ void block_sort(u64* s, int np2) {      // bitonic, np2 a power of two <= SORT_CAP, all QBLOCK threads
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < np2; i += QBLOCK) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const u64 a = s[i], b = s[p];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
-                        s[i] = b;
-                        s[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// x_(rank) of the keys list(0) .. list(len - 1) that lie in [0, top], by one workgroup: sorted in LDS when they fit, narrowed
-// by 1024-bin histograms over the list itself until they do (heavy ties) or one key is left.  `list` is any accessor: the
-// contiguous candidate list of the single-GPU path, or the padded per-rank pieces of the sharded one (padding = ~0 > top).
-// (`short_list`, when given: set if the keys gathered for the sort are not as many as were counted a moment earlier -- a
-// slot allocation lost, as the copy pass of the pilot form once did; the caller refuses the result.)
-template <class List>
-__device__ u64 select_from(const List& list, u64 len, u64 rank, u64 top, int* short_list = nullptr) {
-    __shared__ u64 keys[SORT_CAP];
-    __shared__ unsigned hist[1024];
-    __shared__ u64 s_lo, s_hi, s_cnt, s_rank;
-    __shared__ int s_bin;
-    u64 lo = 0, hi = top;
-    for (;;) {
-        // the keys of the list inside [lo, hi]: how many, their smallest and largest
-        if (threadIdx.x == 0) {
-            s_lo = ~0ull;
-            s_hi = 0;
-            s_cnt = 0;
-        }
-        __syncthreads();
-        u64 mn = ~0ull, mx = 0, cnt = 0;
-        for (u64 i = threadIdx.x; i < len; i += QBLOCK) {
-            const u64 k = list(i);
-            if (k >= lo && k <= hi) {
-                mn = k < mn ? k : mn;
-                mx = k > mx ? k : mx;
-                ++cnt;
-            }
-        }
-        if (cnt) {
-            atomicMin(&s_lo, mn);
-            atomicMax(&s_hi, mx);
-            atomicAdd(&s_cnt, cnt);
-        }
-        __syncthreads();
-        lo = s_lo;
-        hi = s_hi;
-        const u64 inside = s_cnt;
-        __syncthreads();
-        if (lo >= hi) return lo;               // one value left (or, defensively, nothing)
-        if (inside <= SORT_DIRECT) {
-            int np2 = 1;
-            while (np2 < (int)inside) np2 <<= 1;
-            if (threadIdx.x == 0) s_cnt = 0;
-            for (int i = threadIdx.x; i < np2; i += QBLOCK) keys[i] = ~0ull;
-            __syncthreads();
-            for (u64 i = threadIdx.x; i < len; i += QBLOCK) {
-                const u64 k = list(i);
-                if (k >= lo && k <= hi) keys[atomicAdd(&s_cnt, 1ull)] = k;
-            }
-            __syncthreads();
-            if (short_list && threadIdx.x == 0 && s_cnt != inside) atomicExch(short_list, 1);
-            block_sort(keys, np2);
-            const u64 r = keys[rank < inside ? rank : inside - 1];
-            __syncthreads();
-            return r;
-        }
-        // more keys than a short sort takes (or than LDS holds): 1024-bin histogram over [lo, hi], keep the bin that holds the rank
-        for (int i = threadIdx.x; i < 1024; i += QBLOCK) hist[i] = 0;
-        __syncthreads();
-        const double inv = 1024.0 / ((double)(hi - lo) + 1.0);
-        for (u64 i = threadIdx.x; i < len; i += QBLOCK) {
-            const u64 k = list(i);
-            if (k >= lo && k <= hi) atomicAdd(&hist[bin_of_d(k, lo, inv, 1024)], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {                // the bin that holds the rank: one wave, 16 bins per lane, a scan over the lanes' sums
-            const int lane = threadIdx.x;
-            u64 mine = 0;
-#pragma unroll
-            for (int b = 0; b < 16; ++b) mine += hist[16 * lane + b];
-            u64 incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const u64 up = __shfl_up(incl, d);
-                if (lane >= d) incl += up;
-            }
-            const u64 before = incl - mine;
-            // the first lane whose running total exceeds the rank owns it (the last lane, defensively, if none does)
-            const bool owns = incl > rank && before <= rank;
-            const u64 any = __ballot(owns);
-            if (any ? owns : lane == 63) {
-                u64 cum = before;
-                int b = 16 * lane;
-                for (; b < 16 * lane + 15; ++b) {
-                    if (cum + hist[b] > rank) break;
-                    cum += hist[b];
-                }
-                s_bin = b;
-                s_rank = rank - cum;
-            }
-        }
-        __syncthreads();
-        const int keep = s_bin;
-        rank = s_rank;
-        // the keys of that bin form an interval of keys (monotone binning): its ends are found by the next round's min / max
-        if (threadIdx.x == 0) {
-            s_lo = ~0ull;
-            s_hi = 0;
-        }
-        __syncthreads();
-        mn = ~0ull;
-        mx = 0;
-        for (u64 i = threadIdx.x; i < len; i += QBLOCK) {
-            const u64 k = list(i);
-            if (k >= lo && k <= hi && bin_of_d(k, lo, inv, 1024) == keep) {
-                mn = k < mn ? k : mn;
-                mx = k > mx ? k : mx;
-            }
-        }
-        if (mn <= mx) {
-            atomicMin(&s_lo, mn);
-            atomicMax(&s_hi, mx);
-        }
-        __syncthreads();
-        lo = s_lo;
-        hi = s_hi;
-        __syncthreads();
-    }
-}
-
 // (`incomplete`: a list whose copy pass delivered another number of values than the histogram counted -- the two passes bin
 // the same way, so this says the code is wrong, not the data; the host refuses the result.  It has happened: a version of
 // compact_bracket_kernel that parked its hits in LDS lost one value in a few thousand -- percentiles one rank off, in some runs;
@@ -770,11 +457,6 @@ __global__ void brackets_kernel(int m, int nq, const Target* __restrict__ ptg, P
     if (single) atomicExch(any_single, 1);
 }
 
-// the high word of key_of(x) from the high word of x alone (three instructions; the passes below decide nearly every value on it)
-__device__ __forceinline__ unsigned key_high(double x) {
-    const int bh = __double2hiint(x);
-    return (unsigned)bh ^ ((unsigned)(bh >> 31) | 0x80000000u);
-}
 // the smallest t in [0, words + 1] whose bin is >= b (words + 1: none) -- the binning is monotone, so this is where sub-bin b begins
 __device__ __forceinline__ u64 first_t_of_bin(unsigned mult, int b, unsigned words) {
     u64 lo = 0, hi = (u64)words + 1;
@@ -1024,342 +706,161 @@ __global__ void premask_bounds_kernel(int m, int nq, const Bracket* __restrict__
     thr[c] = make_uint4(key_high(lo_min), key_high(lo_max), key_high(hi_min), key_high(hi_max));
 }
 
-// the records the producer wrote are the values the record histogram counted (sums: record_reduce_kernel's)
-__global__ void record_total_check_kernel(const u64* __restrict__ sums, int* __restrict__ inconsistent, const int* __restrict__ prod_flags) {
-    // (a run the producer flagged -- overflow, a non-finite value -- is discarded anyway, and its records need not add up)
-    if (threadIdx.x == 0 && sums[0] != sums[1] && !prod_flags[0] && !prod_flags[1]) atomicExch(inconsistent, -1);
-}
-
-constexpr int REC_LISTS_MAX = 64 * 2 * PEM_QUANTILE_MAX_Q;     // (column, quantile) pairs the record kernels keep a table of (m <= 128)
-
-// the list (column * nq + quantile) of a record: the bracket of its column whose high words hold the key's (they do not overlap)
-template <int NQ>
-__device__ __forceinline__ int record_list(const uint4* __restrict__ s_br, const pem::Record& e, unsigned& t, unsigned& mult, bool& none) {
-    const unsigned kh = (unsigned)(e.key >> 32);
-    const int c0 = (int)e.col * NQ;
-    int cq = c0;
-    uint4 b[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) b[q] = s_br[c0 + q];
-    t = kh - b[0].x;
-    mult = b[0].z;
-    none = t > b[0].y;
-#pragma unroll
-    for (int q = 1; q < NQ; ++q) {
-        const unsigned tq = kh - b[q].x;
-        if (tq <= b[q].y) {
-            cq = c0 + q;
-            t = tq;
-            mult = b[q].z;
-            none = false;
-        }
-    }
-    return cq;
-}
-
-constexpr int REC_UNROLL = 4;   // records a thread has in flight
-
-// (the record passes run one workgroup per CU -- its histogram takes the CU's LDS -- so the workgroup is 1024 threads: with 256 the
-// passes were latency-bound at 2.5 TB/s over the records)
-constexpr int RBLOCK = 1024;
-template <int NQ>
-__global__ __launch_bounds__(RBLOCK) void record_hist_kernel(const pem::Record* __restrict__ rec, const unsigned* __restrict__ rec_count, unsigned cap,
-                                                              unsigned waves, const Bracket* __restrict__ br, int lists, int bins,
-                                                              unsigned* __restrict__ hist) {
-    extern __shared__ unsigned lds_hist[];                      // [lists][bins]
-    __shared__ uint4 s_br[REC_LISTS_MAX];                       // {loh, words, mult, -}
-    for (int i = threadIdx.x; i < lists * bins; i += RBLOCK) lds_hist[i] = 0;
-    for (int i = threadIdx.x; i < lists; i += RBLOCK) s_br[i] = make_uint4(br[i].loh, br[i].words, br[i].mult, 0u);
-    __syncthreads();
-    for (unsigned w = blockIdx.x; w < waves; w += gridDim.x) {
-        const unsigned cnt = rec_count[w] < cap ? rec_count[w] : cap;
-        const pem::Record* r = rec + (size_t)w * cap;
-        for (unsigned i0 = threadIdx.x; i0 < cnt; i0 += RBLOCK * REC_UNROLL) {
-            pem::Record e[REC_UNROLL];
-#pragma unroll
-            for (int u = 0; u < REC_UNROLL; ++u) e[u] = r[i0 + u * RBLOCK < cnt ? i0 + u * RBLOCK : i0];
-#pragma unroll
-            for (int u = 0; u < REC_UNROLL; ++u) {
-                unsigned t, mult;
-                bool none;
-                const int cq = record_list<NQ>(s_br, e[u], t, mult, none);
-                // (none: not a value of any bracket -- a NaN's bits; the producer has flagged the run)
-                if (!none && i0 + u * RBLOCK < cnt) atomicAdd(&lds_hist[cq * bins + (int)__umulhi(t, mult)], 1u);
-            }
-        }
-    }
-    __syncthreads();
-    // the workgroup's own counts, whole (no atomics): summed over the workgroups by record_reduce_kernel, and read again -- per chosen
-    // sub-bin -- by record_offsets_kernel, which gives every workgroup its own place in every list
-    unsigned* mine = hist + (size_t)blockIdx.x * lists * bins;
-    for (int i = threadIdx.x; i < lists * bins; i += RBLOCK) mine[i] = lds_hist[i];
-}
-
-// 64 cells x 4 slices of the workgroups per block, eight loads in flight per thread (one thread per cell walking the 256 partial
-// histograms took 60-120 us of the critical path for 30 MB); the histogram's total and the producer's record count ride along
-// (sums[0], sums[1]: record_total_check_kernel compares them)
-__global__ __launch_bounds__(256) void record_reduce_kernel(const unsigned* __restrict__ part, int groups, int cells, unsigned* __restrict__ hist,
-                                                            const unsigned* __restrict__ rec_count, unsigned cap, unsigned waves,
-                                                            u64* __restrict__ sums) {
-    __shared__ unsigned s_part[4][64];
-    __shared__ u64 s_tot;
-    const int cx = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + cx;
-    if (threadIdx.x == 0) s_tot = 0;
-    unsigned sum = 0;
-    if (i < cells) {
-        int g = slice;
-        for (; g + 28 < groups; g += 32) {
-            unsigned v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(g + 4 * u) * cells + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += v[u];
-        }
-        for (; g < groups; g += 4) sum += part[(size_t)g * cells + i];
-    }
-    s_part[slice][cx] = sum;
-    __syncthreads();
-    if (slice == 0) {
-        const unsigned all = s_part[0][cx] + s_part[1][cx] + s_part[2][cx] + s_part[3][cx];
-        if (i < cells) {
-            hist[i] = all;
-            atomicAdd(&s_tot, (u64)all);
-        }
-    }
-    if (blockIdx.x == 0) {
-        u64 r = 0;
-        for (unsigned w = threadIdx.x; w < waves; w += 256) r += rec_count[w] < cap ? rec_count[w] : cap;
-        if (r) atomicAdd(&sums[1], r);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_tot) atomicAdd(&sums[0], s_tot);
-}
-
-// One wave per target that owns a list: where each workgroup of the copy pass appends its hits -- the exclusive prefix, over the
-// workgroups, of their counts in the list's sub-bin (record_hist_kernel's own histograms).  The copy pass then needs no global
-// atomic (it drew one per hit: 5.6e5 returning atomics on 910 addresses, 0.36 ms for 580 MB of records).
-__global__ __launch_bounds__(64) void record_offsets_kernel(int nt, int bins, const Target* __restrict__ tg, const unsigned* __restrict__ part,
-                                                             int groups, int cells, unsigned* __restrict__ woff) {
-    const int i = blockIdx.x, lane = threadIdx.x, targets = gridDim.x;
-    const Target T = tg[i];
-    const int t = i % nt;
-    const bool own = !T.done && T.owner == t;
-    const int cell = (i / 2) * bins + (own ? T.bin2 : 0);      // targets 2q, 2q + 1 of column c belong to list c nq + q = i / 2
-    unsigned base = 0;
-    for (int g0 = 0; g0 < groups; g0 += 64) {
-        const int g = g0 + lane;
-        const unsigned v = (own && g < groups) ? part[(size_t)g * cells + cell] : 0u;
-        unsigned incl = v;
-#pragma unroll
-        for (int sh = 1; sh < 64; sh <<= 1) {
-            const unsigned up = __shfl_up(incl, sh);
-            if (lane >= sh) incl += up;
-        }
-        if (g < groups) woff[(size_t)g * targets + i] = base + incl - v;
-        base += __shfl(incl, 63);
-    }
-}
-
-template <int NQ>
-__global__ __launch_bounds__(RBLOCK) void record_compact_kernel(const pem::Record* __restrict__ rec, const unsigned* __restrict__ rec_count, unsigned cap,
-                                                                 unsigned waves, const Bracket* __restrict__ br, int lists, Target* __restrict__ tg,
-                                                                 const unsigned* __restrict__ woff, u64* __restrict__ cand) {
-    __shared__ uint4 s_br[REC_LISTS_MAX];                       // {loh, words, mult, -}
-    __shared__ int2 s_bin[REC_LISTS_MAX];                       // the sub-bins the quantile's two targets collect (-1: not a list owner)
-    __shared__ unsigned s_cur[2 * REC_LISTS_MAX];               // this workgroup's cursor in every target's list (from record_offsets_kernel)
-    __shared__ u64 s_base[2 * REC_LISTS_MAX];                   // the lists' starts in `cand`
-    const unsigned* my_off = woff + (size_t)blockIdx.x * 2 * lists;
-    for (int i = threadIdx.x; i < lists; i += RBLOCK) {
-        s_br[i] = make_uint4(br[i].loh, br[i].words, br[i].mult, 0u);
-        const Target &T0 = tg[2 * i], &T1 = tg[2 * i + 1];     // targets 2q, 2q + 1 of column c sit at (c nq + q) 2
-        s_bin[i] = make_int2((!T0.done && (T0.owner & 1) == 0) ? T0.bin2 : -1, (!T1.done && (T1.owner & 1) == 1) ? T1.bin2 : -1);
-        s_cur[2 * i] = my_off[2 * i];
-        s_cur[2 * i + 1] = my_off[2 * i + 1];
-        s_base[2 * i] = T0.offset;
-        s_base[2 * i + 1] = T1.offset;
-    }
-    __syncthreads();
-    // (the same records as this workgroup counted in record_hist_kernel: same grid, same walk)
-    for (unsigned w = blockIdx.x; w < waves; w += gridDim.x) {
-        const unsigned cnt = rec_count[w] < cap ? rec_count[w] : cap;
-        const pem::Record* r = rec + (size_t)w * cap;
-        for (unsigned i0 = threadIdx.x; i0 < cnt; i0 += RBLOCK * REC_UNROLL) {
-            pem::Record e[REC_UNROLL];
-#pragma unroll
-            for (int u = 0; u < REC_UNROLL; ++u) e[u] = r[i0 + u * RBLOCK < cnt ? i0 + u * RBLOCK : i0];
-#pragma unroll
-            for (int u = 0; u < REC_UNROLL; ++u) {
-                unsigned t, mult;
-                bool none;
-                const int cq = record_list<NQ>(s_br, e[u], t, mult, none);
-                if (none || i0 + u * RBLOCK >= cnt) continue;
-                const int bin = (int)__umulhi(t, mult);
-                const int2 want = s_bin[cq];
-                const int hit = want.x == bin ? 0 : (want.y == bin ? 1 : -1);
-                if (hit >= 0) cand[s_base[2 * cq + hit] + atomicAdd(&s_cur[2 * cq + hit], 1u)] = e[u].key;
-            }
-        }
-    }
-    __syncthreads();
-    // what this workgroup appended, onto the lists' counters: select_kernel compares them with the counts (the "incomplete" check)
-    for (int i = threadIdx.x; i < 2 * lists; i += RBLOCK) {
-        const unsigned wrote = s_cur[i] - my_off[i];
-        if (wrote) atomicAdd(&tg[i].cursor, (u64)wrote);
-    }
-}
-
-// ---- the multi-rank form: histograms over caller-given key ranges -----------------------------------------------------------
-// Samples sharded over ranks cannot be copied out and sorted in one place cheaply, but histograms add: every rank counts its
-// own values inside the current range of every wanted rank, the counts are all-reduced (<= 144 KB), all ranks pick the same
-// bin and narrow the range to it -- until a range is one key (hallthrusterpem_amd/percentiles.py drives the levels).
-// Range r of column c: keys klo[c][r] .. khi[c][r]; d = (k - klo) >> shift with shift such that the span fits 31 bits;
-// bin = d when the shifted span is smaller than `bins` (every key its own bin: the next range is a single key), else
-// floor(d mult / 2^32), mult = min(2^32 - 1, floor(2^32 bins / (span' + 1))).  percentiles.py inverts exactly this map.
-struct RangeScale {
-    u64 lo, hi;
-    unsigned mult;
-    int shift, identity;
-};
-__device__ __forceinline__ RangeScale range_scale(u64 lo, u64 hi, int bins) {
-    RangeScale r;
-    r.lo = lo;
-    r.hi = hi;
-    const u64 span = hi >= lo ? hi - lo : 0;
-    int shift = 0;
-    while ((span >> shift) >> 31) ++shift;
-    const u64 d = span >> shift;
-    r.shift = shift;
-    r.identity = d < (u64)bins;
-    const u64 mult = (((u64)bins) << 32) / (d + 1);
-    r.mult = mult > 0xffffffffull ? 0xffffffffu : (unsigned)mult;
-    return r;
-}
-
-template <int NC, int NR>
-__global__ __launch_bounds__(QBLOCK) void range_hist_kernel(long long n, int m, size_t ld, const double* __restrict__ data,
-                                                             const u64* __restrict__ klo, const u64* __restrict__ khi, int bins,
-                                                             unsigned* __restrict__ hist) {
-    extern __shared__ unsigned lds_hist[];
-    for (int i = threadIdx.x; i < m * NR * bins; i += QBLOCK) lds_hist[i] = 0;
-    __syncthreads();
-    const Lanes L(m, threadIdx.x & 63);
-    RangeScale rs[NC][NR];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = L.col0 + 64 * j;
-        const bool on = L.active && c < m;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) rs[j][r] = on ? range_scale(klo[c * NR + r], khi[c * NR + r], bins) : range_scale(1, 0, bins);
-    }
-    stream_values<NC, (NC >= 4 && NR >= 4) ? 2 : UNROLL>(n, m, ld, data, L, [&](int j, int c, double x) {
-        if (x == x) {
-            const u64 k = key_of(x);
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const RangeScale& q = rs[j][r];
-                if (k >= q.lo && k <= q.hi) {
-                    const unsigned d = (unsigned)((k - q.lo) >> q.shift);
-                    const int b = q.identity ? (int)d : (int)(((u64)d * q.mult) >> 32);
-                    atomicAdd(&lds_hist[(c * NR + r) * bins + b], 1u);
-                }
-            }
-        }
-    });
-    __syncthreads();
-    for (int i = threadIdx.x; i < m * NR * bins; i += QBLOCK) {
-        const unsigned v = lds_hist[i];
-        if (v) atomicAdd(&hist[i], v);
-    }
-}
-
-// One level's decision on the device (one wave per range): the bin of the all-reduced histogram that holds the wanted rank,
-// and the keys of that bin -- the inverse of range_scale's map, as percentiles.bin_interval states it -- become the next range.
-__global__ __launch_bounds__(64) void range_narrow_kernel(int bins, const unsigned* __restrict__ hist, u64* __restrict__ klo,
-                                                           u64* __restrict__ khi, long long* __restrict__ resid) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const u64 lo = klo[i], hi = khi[i];
-    if (lo >= hi) return;                                     // already one key (or an empty column)
-    const Found f = find_bin(hist + (size_t)i * bins, bins, (u64)resid[i], lane);
-    if (lane != 0) return;
-    const RangeScale q = range_scale(lo, hi, bins);
-    const u64 b = (u64)f.bin, two32 = 1ull << 32;
-    const u64 d_lo = q.identity ? b : (b * two32 + q.mult - 1) / q.mult;
-    const u64 d_hi = q.identity ? b : ((b + 1) * two32 + q.mult - 1) / q.mult - 1;
-    const bool last = d_hi >= ((hi - lo) >> q.shift);
-    u64 nlo = lo + (d_lo << q.shift);
-    u64 nhi = last ? hi : lo + (((d_hi + 1) << q.shift) - 1);
-    if (nlo < lo) nlo = lo;
-    if (nhi > hi) nhi = hi;
-    klo[i] = nlo;
-    khi[i] = nhi;
-    resid[i] -= (long long)f.before;
-}
-
-__global__ void export_minmax_kernel(const Column* __restrict__ col, int m, u64* kmin, u64* kmax, int* has_nan) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m) {
-        kmin[c] = col[c].kmin;
-        kmax[c] = col[c].kmax;
-        has_nan[c] = col[c].has_nan ? 1 : 0;
-    }
-}
-
-int pow2_at_most(long long x, int cap) {
-    int p = 1;
-    while (2LL * p <= x && 2 * p <= cap) p <<= 1;
-    return p;
-}
-
 }  // namespace
+
+#include "pem_quantile_records.h"
 
 // which way the last call of pem_quantiles_f64_dev went: 0 four passes, 1 pilot + two passes, 2 pilot, then four passes (a
 // wanted rank outside its bracket)
 static std::atomic<int> g_last_path{0};
 extern "C" int pem_quantiles_last_path(void) { return g_last_path.load(); }
 
-// `fused` (with `fused_ok`): the array does not exist (yet) -- `data` are its first ceil(n / pilot) rows, written by the producer,
-// and pass A / pass B are the producer's counting launch and two passes over its records (csrc/pem_qfused.h).  *fused_ok = 0: the
-// brackets were unfit for the producer, a rank fell outside its bracket, or the producer reported an overflow or a non-finite
-// sample -- `out` is then not written and the caller takes the passes over the array itself.
+// ---- the host's side: one call is validate -> plan -> workspace -> (pilot brackets -> counting pass -> copy pass | four passes) -> finish
+namespace {
+
+// A device buffer kept between calls.  It only grows: a hipFree + hipMalloc in the middle of a call costs a device synchronisation
+// and a millisecond.
+template <class T>
+struct DeviceBuffer {
+    T* ptr = nullptr;
+    size_t cap = 0;                            // elements
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+    hipError_t reserve(size_t need, size_t room) {      // at least `need` elements; `room` of them when it has to grow
+        if (cap >= need) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc(&ptr, room * sizeof(T));
+        if (e == hipSuccess) cap = room;
+        return e;
+    }
+};
+
 // The buffers a selection keeps between calls (grow-only).  Two sets: calls are serialised on a set, and the second one lets the
 // scalar QoIs of a campaign be selected on another host thread and stream while the fused form is busy with the profile's records.
-namespace {
 struct QWork {
     std::mutex mu;
-    char* ws_buf = nullptr;
-    size_t ws_cap = 0, cand_cap = 0, rec_cap = 0;
-    u64* cand_buf = nullptr;
-    pem::Record* rec_buf = nullptr;
-    unsigned* part_buf = nullptr;              // fused form: the record histograms of every workgroup | their offsets into the lists
-    size_t part_cap = 0;
-    int ws_dev = -1;
+    int dev = -1;                              // the device the buffers live on: all of them are freed when it changes
+    DeviceBuffer<char> ws;                     // the workspace (Selection::lay_out)
+    DeviceBuffer<u64> cand;                    // the candidate lists
+    DeviceBuffer<pem::Record> rec;             // fused form: the producer's records
+    DeviceBuffer<unsigned> part;               // fused form: the record histograms of every workgroup | their offsets into the lists
 };
 QWork g_qwork[2];
-}  // namespace
 
-static int quantiles_impl(size_t n, int m, const double* data, size_t ld, size_t cs, int nq, const uint64_t* rank_prev,
-                          const uint64_t* rank_next, const double* gamma, double* out, pem_stream_t stream, pem::FusedProducer* fused,
-                          int* fused_ok, int slot = 0, const pem::SidePlan* plan = nullptr) {
+// The words the kernels report through: 256 bytes of the workspace behind hist2, zeroed with the histograms (four passes) or on
+// their own (pilot form).  The kernels get the addresses of single members; the host reads the groups back whole.
+struct Flags {
+    struct Counted {
+        u64 candidates;                        // layout_kernel: the length of all candidate lists
+        int outside, pad;                      // decide_bracket_kernel: a wanted rank lies outside its bracket
+    } counted;
+    u64 incomplete[4];                         // select_kernel: [0] (as int) a list shorter or longer than counted, or sorted with fewer keys;
+                                               // then which list, the values it was given, the values counted
+    u64 unused[2];
+    int any_single, pad;                       // brackets_kernel: a bracket of one key exists
+    struct Fused {                             // fused form
+        int unfit;                             // bracket_check_kernel: brackets a producer cannot count against
+        int prod_flags[2];                     // the producer's: a wave's record region overflowed | a non-finite sample
+        int pm_bad;                            // premask_bounds_kernel: the premask's bounds are unfit
+    } fused;
+    int inconsistent;                          // a histogram's total is not the number of values counted: 1 + column (decide1_kernel),
+                                               // -1 the record histogram (record_total_check_kernel)
+    int pad2[9];
+    u64 rec_sums[2];                           // record_reduce_kernel: the record histogram's total | the producer's record count
+};
+static_assert(offsetof(Flags, incomplete) == 16 && offsetof(Flags, any_single) == 64 && offsetof(Flags, fused) == 72 &&
+                  offsetof(Flags, inconsistent) == 88 && offsetof(Flags, rec_sums) == 128 && sizeof(Flags) <= 256,
+              "the kernels' flag words keep their places in the workspace");
+
+// One call.  `fused` (with `fused_ok`): the array does not exist (yet) -- `data` are its first ceil(n / pilot) rows, written by the
+// producer, and pass A / pass B are the producer's counting launch and two passes over its records (csrc/pem_qfused.h).
+// *fused_ok = 0: the brackets were unfit for the producer, a rank fell outside its bracket, or the producer reported an overflow or
+// a non-finite sample -- `out` is then not written and the caller takes the passes over the array itself.
+struct Selection {
+    // the data and what is wanted of it
+    size_t n;
+    int m;
+    const double* data;
+    size_t ld, cs;
+    int nq;
+    double* out;
+    hipStream_t st;
+    pem::FusedProducer* fused;
+    int* fused_ok;
+    int slot;
+    const pem::SidePlan* plan;
+    Wanted w{};
+    int nt = 0, nc = 0;                        // targets per column, columns per lane
+    // the plan
+    int bins1 = 0, bins2 = 0, binsA = 0;       // bins of the two histograms; of the pilot form's histogram inside a bracket
+    long long pilot = 0;                       // the subsample's stride
+    bool use_pilot = false;
+    unsigned fused_waves = 0;                  // waves of the producer's counting launch
+    // the workspace: columns | targets | hist1 | hist2 | flags | brackets | below | histA | record counts | premask bounds
+    QWork* work = nullptr;
+    Column* col = nullptr;
+    Target* tg = nullptr;
+    unsigned *hist1 = nullptr, *hist2 = nullptr;
+    Flags* flags = nullptr;
+    Bracket* br = nullptr;
+    u64* below = nullptr;
+    unsigned* histA = nullptr;
+    unsigned* rec_count = nullptr;
+    uint4* pm_thr = nullptr;
+    size_t hists_and_flags = 0, counts = 0;    // bytes from hist1 to the end of the flags, and from `below` to the end
+    int path = 0;                              // pem_quantiles_last_path
+
+    // every error return waits for the stream: the workspace belongs to the next call as soon as this one gives up the lock
+    int cleanup(int code) const {
+        (void)hipStreamSynchronize(st);
+        return code;
+    }
+    size_t lay_out(char* ws);
+};
+
+// HIP_TRY for the steps of a Selection `q` (after the workspace is in use: with cleanup)
+#define Q_TRY(expr)                                                                                            \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return q.cleanup(pem::fail(PEM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); \
+    } while (0)
+
+int validate(Selection& q, const uint64_t* rank_prev, const uint64_t* rank_next, const double* gamma) {
+    const size_t n = q.n, ld = q.ld, cs = q.cs;
+    const int m = q.m, nq = q.nq;
     if (m < 1 || m > 64 * MAX_NC) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: 1 <= m <= %d columns", 64 * MAX_NC);
-    if (fused && (m > 128 || !fused_ok)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: the fused form takes up to 128 columns");
+    if (q.fused && (m > 128 || !q.fused_ok)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: the fused form takes up to 128 columns");
     if (cs < 1 || (cs == 1 ? ld < (size_t)m : (ld != 1 || cs < n)))
         return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: rows of m columns (column stride 1, ld >= m) or columns of n rows (ld 1, column stride >= n)");
     if (nq < 1 || nq > (m <= 128 ? PEM_QUANTILE_MAX_Q : PEM_QUANTILE_MAX_Q_WIDE))
         return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: 1 <= nq <= %d per call (%d for more than 128 columns)", PEM_QUANTILE_MAX_Q, PEM_QUANTILE_MAX_Q_WIDE);
     if (n == 0) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: no samples");
-    if (!data || !rank_prev || !rank_next || !gamma || !out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: NULL array");
-    for (int q = 0; q < nq; ++q)
-        if (rank_prev[q] >= n || rank_next[q] >= n || rank_prev[q] > rank_next[q])
+    if (!q.data || !rank_prev || !rank_next || !gamma || !q.out) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: NULL array");
+    for (int i = 0; i < nq; ++i) {
+        if (rank_prev[i] >= n || rank_next[i] >= n || rank_prev[i] > rank_next[i])
             return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: ranks must satisfy prev <= next < n");
-    if (int rc = pem::check_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nt = 2 * nq;
-    const int bins1 = pow2_at_most(LDS_WORDS / m, 4096), bins2 = pow2_at_most(LDS_WORDS / (m * nt), 4096);
+        q.w.prev[i] = rank_prev[i];
+        q.w.next[i] = rank_next[i];
+        q.w.gamma[i] = gamma[i];
+    }
+    q.nt = 2 * nq;
+    q.nc = columns_per_lane(m);
+    return pem::check_device();
+}
+
+// bins, the pilot choice and the environment's overrides (read on every call)
+int plan_selection(Selection& q) {
+    const int m = q.m, nq = q.nq;
+    const long long n = (long long)q.n;
+    q.bins1 = pow2_at_most(LDS_WORDS / m, 4096);
+    q.bins2 = pow2_at_most(LDS_WORDS / (m * q.nt), 4096);
     // (four quantiles or more: the brackets' registers leave room for one workgroup per CU anyway -- it gets all of the LDS)
-    int binsA = pow2_at_most((m <= 128 ? LDS_WORDS_A : LDS_WORDS) / (m * nq) - 1, 4096);   // the pilot form's histogram inside a bracket (+ 1 counter)
-    if (fused) binsA = pow2_at_most(LDS_WORDS / (m * nq), 4096);          // (the record passes: one workgroup per CU with all of its LDS)
-    if (const char* e = getenv("PEM_QUANTILE_BINSA")) binsA = pow2_at_most(atoll(e) < binsA ? atoll(e) : binsA, 4096);
+    q.binsA = pow2_at_most((m <= 128 ? LDS_WORDS_A : LDS_WORDS) / (m * nq) - 1, 4096);   // the pilot form's histogram inside a bracket (+ 1 counter)
+    if (q.fused) q.binsA = pow2_at_most(LDS_WORDS / (m * nq), 4096);        // (the record passes: one workgroup per CU with all of its LDS)
+    if (const char* e = getenv("PEM_QUANTILE_BINSA")) q.binsA = pow2_at_most(atoll(e) < q.binsA ? atoll(e) : q.binsA, 4096);
 
     // the pilot form: every `pilot`-th row brackets the wanted ranks (PEM_QUANTILE_PILOT: the stride, 0 = never;
     // PEM_QUANTILE_PILOT_MIN: the smallest n * m it is used for -- 1e7 x 1 takes 0.24 ms with the four passes and 0.32 with the
@@ -1367,383 +868,285 @@ static int quantiles_impl(size_t n, int m, const double* data, size_t ld, size_t
     long long pilot = 32, pilot_min = 1 << 25;
     if (const char* e = getenv("PEM_QUANTILE_PILOT")) pilot = atoll(e);
     if (const char* e = getenv("PEM_QUANTILE_PILOT_MIN")) pilot_min = atoll(e);
-    if (fused) {                                                          // (the producer writes rows 0 .. ceil(n / 32) - 1 at most)
+    if (q.fused) {                                                          // (the producer writes rows 0 .. ceil(n / 32) - 1 at most)
         pilot = 32;
         if (const char* e = getenv("PEM_FUSED_PILOT")) pilot = atoll(e) >= 32 ? atoll(e) : 32;
     }
-    if (plan) pilot = 32;                                                 // (the rows the plan's caller has written: 0 .. ceil(n / 32) - 1)
-    const bool use_pilot = fused ? true : plan ? (long long)n >= 4 * pilot : (pilot >= 2 && (long long)n * m >= pilot_min && (long long)n >= 4 * pilot);
-    if (fused && (long long)n < 4 * pilot) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: the fused form needs at least %lld rows", 4 * pilot);
+    if (q.plan) pilot = 32;                                                 // (the rows the plan's caller has written: 0 .. ceil(n / 32) - 1)
+    q.pilot = pilot;
+    q.use_pilot = q.fused ? true : q.plan ? n >= 4 * pilot : (pilot >= 2 && n * m >= pilot_min && n >= 4 * pilot);
+    if (q.fused && n < 4 * pilot) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: the fused form needs at least %lld rows", 4 * pilot);
+    if (q.fused) return q.fused->waves(nq, &q.fused_waves);
+    return PEM_OK;
+}
 
-    // workspace: columns | targets | hist1 | hist2 | total, outside | brackets | below | histA -- kept between calls (grow-only,
-    // one per process; calls are serialised on it, and each one ends with a stream synchronisation before the next may touch it)
-    const size_t b_col = sizeof(Column) * m, b_tg = sizeof(Target) * m * nt;
-    const size_t b_h1 = sizeof(unsigned) * (size_t)m * bins1, b_h2 = sizeof(unsigned) * (size_t)m * nt * bins2;
-    const size_t b_br = sizeof(Bracket) * m * nq, b_bl = sizeof(u64) * m * nq, b_hA = sizeof(unsigned) * (size_t)m * nq * binsA;
+// the workspace's parts at `ws` (nullptr: only their total size is wanted)
+size_t Selection::lay_out(char* ws) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_tg = up(b_col), o_h1 = o_tg + up(b_tg), o_h2 = o_h1 + up(b_h1), o_tot = o_h2 + up(b_h2);
-    unsigned fused_waves = 0;
-    if (fused)
-        if (int rc = fused->waves(nq, &fused_waves)) return rc;
-    const size_t b_rc = sizeof(unsigned) * fused_waves;
-    const size_t o_br = o_tot + 256, o_bl = o_br + up(b_br), o_hA = o_bl + up(b_bl), o_rc = o_hA + up(b_hA), o_pm = o_rc + up(b_rc);
+    const size_t o_tg = up(sizeof(Column) * m), o_h1 = o_tg + up(sizeof(Target) * m * nt);
+    const size_t o_h2 = o_h1 + up(sizeof(unsigned) * (size_t)m * bins1), o_fl = o_h2 + up(sizeof(unsigned) * (size_t)m * nt * bins2);
+    const size_t o_br = o_fl + 256, o_bl = o_br + up(sizeof(Bracket) * m * nq), o_hA = o_bl + up(sizeof(u64) * m * nq);
+    const size_t o_rc = o_hA + up(sizeof(unsigned) * (size_t)m * nq * binsA), o_pm = o_rc + up(sizeof(unsigned) * fused_waves);
     const size_t o_end = o_pm + up(sizeof(uint4) * (size_t)m);
-    QWork& work = g_qwork[slot];
-    std::lock_guard<std::mutex> lock(work.mu);
-    char*& ws_buf = work.ws_buf;
-    size_t &ws_cap = work.ws_cap, &cand_cap = work.cand_cap, &rec_cap = work.rec_cap, &part_cap = work.part_cap;
-    u64*& cand_buf = work.cand_buf;
-    pem::Record*& rec_buf = work.rec_buf;
-    unsigned*& part_buf = work.part_buf;
-    int& ws_dev = work.ws_dev;
+    auto at = [ws](size_t o) { return ws ? ws + o : nullptr; };
+    col = reinterpret_cast<Column*>(at(0));
+    tg = reinterpret_cast<Target*>(at(o_tg));
+    hist1 = reinterpret_cast<unsigned*>(at(o_h1));
+    hist2 = reinterpret_cast<unsigned*>(at(o_h2));
+    flags = reinterpret_cast<Flags*>(at(o_fl));
+    br = reinterpret_cast<Bracket*>(at(o_br));
+    below = reinterpret_cast<u64*>(at(o_bl));
+    histA = reinterpret_cast<unsigned*>(at(o_hA));
+    rec_count = reinterpret_cast<unsigned*>(at(o_rc));
+    pm_thr = reinterpret_cast<uint4*>(at(o_pm));
+    hists_and_flags = o_br - o_h1;
+    counts = o_end - o_bl;
+    return o_end;
+}
+
+// the slot's buffers on the current device, the workspace large enough for this call (the caller holds the slot's lock: calls are
+// serialised on it, and each one ends with a stream synchronisation before the next may touch the buffers)
+int size_workspace(Selection& q) {
+    QWork& work = g_qwork[q.slot];
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    if (dev != ws_dev || ws_cap < o_end) {
-        if (ws_buf) (void)hipFree(ws_buf);
-        if (cand_buf && dev != ws_dev) {
-            (void)hipFree(cand_buf);
-            cand_buf = nullptr;
-            cand_cap = 0;
-        }
-        if (rec_buf && dev != ws_dev) {
-            (void)hipFree(rec_buf);
-            rec_buf = nullptr;
-            rec_cap = 0;
-        }
-        if (part_buf && dev != ws_dev) {
-            (void)hipFree(part_buf);
-            part_buf = nullptr;
-            part_cap = 0;
-        }
-        ws_buf = nullptr;
-        ws_cap = 0;
-        HIP_TRY(hipMalloc(&ws_buf, o_end));
-        ws_cap = o_end;
-        ws_dev = dev;
+    if (dev != work.dev) {
+        work.ws.release();
+        work.cand.release();
+        work.rec.release();
+        work.part.release();
+        work.dev = dev;
     }
-    char* ws = ws_buf;
-    Column* col = reinterpret_cast<Column*>(ws);
-    Target* tg = reinterpret_cast<Target*>(ws + o_tg);
-    unsigned* hist1 = reinterpret_cast<unsigned*>(ws + o_h1);
-    unsigned* hist2 = reinterpret_cast<unsigned*>(ws + o_h2);
-    u64* total = reinterpret_cast<u64*>(ws + o_tot);                       // total[0]: candidates; total[1] (as int): a rank outside its bracket
-    int* outside = reinterpret_cast<int*>(total + 1);
-    int* incomplete = reinterpret_cast<int*>(total + 2);                   // a list shorter or longer than counted (select_kernel), 4 words
-    int* any_single = reinterpret_cast<int*>(total + 8);                   // a bracket of one key exists (brackets_kernel)
-    int* unfit = reinterpret_cast<int*>(total + 9);                        // fused form: brackets a producer cannot count against
-    int* prod_flags = unfit + 1;                                           // fused form: the producer's overflow / non-finite flags (2 ints)
-    unsigned* rec_count = reinterpret_cast<unsigned*>(ws + o_rc);
-    uint4* pm_thr = reinterpret_cast<uint4*>(ws + o_pm);
-    int* pm_bad = unfit + 3;                                               // fused form: premask bounds unfit
-    int* inconsistent = unfit + 4;                                         // a histogram's total is not the number of values counted (1 + column)
-    Bracket* br = reinterpret_cast<Bracket*>(ws + o_br);
-    u64* below = reinterpret_cast<u64*>(ws + o_bl);
-    unsigned* histA = reinterpret_cast<unsigned*>(ws + o_hA);
-    auto cleanup = [&](int code) {
-        (void)hipStreamSynchronize(st);
-        return code;
-    };
-#define Q_TRY(expr)                                                                                          \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) return cleanup(pem::fail(PEM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-    } while (0)
+    const size_t bytes = q.lay_out(nullptr);
+    HIP_TRY(work.ws.reserve(bytes, bytes));
+    q.lay_out(work.ws.ptr);
+    q.work = &work;
+    return PEM_OK;
+}
 
-    Wanted w{};
-    for (int q = 0; q < nq; ++q) {
-        w.prev[q] = rank_prev[q];
-        w.next[q] = rank_next[q];
-        w.gamma[q] = gamma[q];
-    }
-    const int cblocks = (m + 63) / 64;
-    const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-    const size_t lds1 = (size_t)m * bins1 * 4, lds2 = (size_t)m * nt * bins2 * 4, ldsA = (size_t)m * nq * (binsA + 1) * 4;
-    const dim3 blk(QBLOCK);
-    auto grid_for = [&](size_t rows) {
-        const long long rpw = m <= 64 ? 64 / m : 1, groups = ((long long)rows + rpw - 1) / rpw;
-        long long blocks = (groups + (long long)QWAVES * UNROLL - 1) / ((long long)QWAVES * UNROLL);
-        if (blocks > 256 * 2) blocks = 256 * 2;
-        return dim3((unsigned)blocks);
-    };
-    auto grow_candidates = [&](u64 need) -> hipError_t {
-        if (cand_cap >= need + 1) return hipSuccess;
-        if (cand_buf) (void)hipFree(cand_buf);
-        cand_buf = nullptr;
-        cand_cap = 0;
-        // (a quarter more than asked for: the lists of two campaigns differ by a few values, and a hipFree + hipMalloc in the middle of
-        // a call costs a device synchronisation and a millisecond)
-        const u64 room = need + need / 4 + 1024;
-        const hipError_t e = hipMalloc(&cand_buf, (size_t)room * sizeof(u64));
-        if (e == hipSuccess) cand_cap = room;
-        return e;
-    };
-#define Q_LDS(KERN) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-#define Q_BY_NC(CALL)              \
-    do {                           \
-        if (nc == 1) { CALL(1); }  \
-        else if (nc == 2) { CALL(2); } \
-        else { CALL(4); }          \
-    } while (0)
-#define Q_BY_NT_SMALL(CALL, NC_)       \
-    do {                               \
-        if (nt == 2) { CALL(NC_, 2); } \
-        else if (nt == 4) { CALL(NC_, 4); } \
-        else { CALL(NC_, 6); }         \
-    } while (0)
-#define Q_BY_NT_ALL(CALL, NC_)         \
-    do {                               \
-        if (nt == 2) { CALL(NC_, 2); } \
-        else if (nt == 4) { CALL(NC_, 4); } \
-        else if (nt == 6) { CALL(NC_, 6); } \
-        else if (nt == 8) { CALL(NC_, 8); } \
-        else if (nt == 10) { CALL(NC_, 10); } \
-        else { CALL(NC_, 12); }        \
-    } while (0)
-#define Q_BY_NQ_SMALL(CALL, NC_)       \
-    do {                               \
-        if (nq == 1) { CALL(NC_, 1); } \
-        else if (nq == 2) { CALL(NC_, 2); } \
-        else { CALL(NC_, 3); }         \
-    } while (0)
-#define Q_BY_NQ_ALL(CALL, NC_)         \
-    do {                               \
-        if (nq == 1) { CALL(NC_, 1); } \
-        else if (nq == 2) { CALL(NC_, 2); } \
-        else if (nq == 3) { CALL(NC_, 3); } \
-        else if (nq == 4) { CALL(NC_, 4); } \
-        else if (nq == 5) { CALL(NC_, 5); } \
-        else { CALL(NC_, 6); }         \
-    } while (0)
-// more than three quantiles per call for up to 128 columns only (four columns per lane run out of registers: Q_MAX_WIDE)
-#define Q_BY_NT_1 Q_BY_NT_ALL
-#define Q_BY_NT_2 Q_BY_NT_ALL
-#define Q_BY_NT_4 Q_BY_NT_SMALL
-#define Q_BY_NQ_1 Q_BY_NQ_ALL
-#define Q_BY_NQ_2 Q_BY_NQ_ALL
-#define Q_BY_NQ_4 Q_BY_NQ_SMALL
+hipError_t grow_candidates(Selection& q, u64 need) {
+    // (a quarter more than asked for: the lists of two campaigns differ by a few values, and a hipFree + hipMalloc in the middle of
+    // a call costs a device synchronisation and a millisecond)
+    return q.work->cand.reserve((size_t)need + 1, (size_t)(need + need / 4 + 1024));
+}
 
-    // the four passes over rows 0, step, 2 step, ... (`rows` of them, leading dimension ldd): x_(rank) of every target ends in tg[].answer
-    // (edges: stop after the second histogram and take the sub-bins' first / last keys as the answers -- pilot_edges_kernel)
-    auto four_passes = [&](size_t rows, size_t ldd, const Wanted& ww, bool edges = false) -> int {
-        const dim3 grid = grid_for(rows);
-        Q_TRY(hipMemsetAsync(hist1, 0, o_tot + 256 - o_h1, st));            // hist1, hist2, total
-        hipLaunchKernelGGL(init_columns_kernel, dim3(cblocks), dim3(64), 0, st, col, tg, m, nq, ww);
-#define Q_MINMAX(NC_) hipLaunchKernelGGL(minmax_kernel<NC_>, grid, blk, 0, st, (long long)rows, m, ldd, cs, data, col)
-        Q_BY_NC(Q_MINMAX);
-        hipLaunchKernelGGL(scale_columns_kernel, dim3(cblocks), dim3(64), 0, st, col, m, bins1);
-#define Q_HIST1(NC_)                                                                                       \
-    Q_LDS(hist1_kernel<NC_>);                                                                              \
-    hipLaunchKernelGGL(hist1_kernel<NC_>, grid, blk, lds1, st, (long long)rows, m, ldd, cs, data, col, bins1, hist1)
-        Q_BY_NC(Q_HIST1);
-        hipLaunchKernelGGL(decide1_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, m, nt, col, hist1, bins1, tg, (long long)rows, inconsistent);
-#define Q_HIST2_(NC_, NT_)                                                                                                  \
-    Q_LDS((hist2_kernel<NC_, NT_>));                                                                                        \
-    hipLaunchKernelGGL((hist2_kernel<NC_, NT_>), grid, blk, lds2, st, (long long)rows, m, ldd, cs, data, col, tg, bins1, bins2, hist2)
-#define Q_HIST2(NC_) Q_BY_NT_##NC_(Q_HIST2_, NC_)
-        Q_BY_NC(Q_HIST2);
-        hipLaunchKernelGGL(decide2_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, nt, hist2, bins2, tg);
-        if (edges) {
-            hipLaunchKernelGGL(pilot_edges_kernel, dim3((unsigned)((m * nt + 63) / 64)), dim3(64), 0, st, m * nt, nt, bins2, col, tg);
-            Q_TRY(hipGetLastError());
-            return PEM_OK;
-        }
-        hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64 * MAX_NC), 0, st, m, nt, tg, total);
-        Q_TRY(hipGetLastError());
-        u64 h_total = 0;
-        Q_TRY(hipMemcpyAsync(&h_total, total, sizeof(u64), hipMemcpyDeviceToHost, st));
-        Q_TRY(hipStreamSynchronize(st));
-        Q_TRY(grow_candidates(h_total));
-        u64* cand = cand_buf;
-#define Q_COMPACT_(NC_, NT_) \
-    hipLaunchKernelGGL((compact_kernel<NC_, NT_>), grid, blk, 0, st, (long long)rows, m, ldd, cs, data, col, tg, bins1, bins2, cand)
-#define Q_COMPACT(NC_) Q_BY_NT_##NC_(Q_COMPACT_, NC_)
-        Q_BY_NC(Q_COMPACT);
-        hipLaunchKernelGGL(select_kernel, dim3((unsigned)(m * nt)), blk, 0, st, nt, tg, cand, incomplete);
+// the four passes over rows 0, step, 2 step, ... (`rows` of them, leading dimension ldd): x_(rank) of every target ends in tg[].answer
+// (edges: stop after the second histogram and take the sub-bins' first / last keys as the answers -- pilot_edges_kernel)
+int four_passes(Selection& q, size_t rows, size_t ldd, const Wanted& ww, bool edges = false) {
+    const int m = q.m, nq = q.nq, nt = q.nt, bins1 = q.bins1, bins2 = q.bins2;
+    hipStream_t st = q.st;
+    const dim3 grid = stream_grid(rows, m), blk(QBLOCK), columns((m + 63) / 64), targets((unsigned)(m * nt));
+    Q_TRY(hipMemsetAsync(q.hist1, 0, q.hists_and_flags, st));              // hist1, hist2, flags
+    hipLaunchKernelGGL(init_columns_kernel, columns, dim3(64), 0, st, q.col, q.tg, m, nq, ww);
+    with_value(q.nc, ColumnCounts{}, [&](auto NC) {
+        hipLaunchKernelGGL(minmax_kernel<NC()>, grid, blk, 0, st, (long long)rows, m, ldd, q.cs, q.data, q.col);
+    });
+    hipLaunchKernelGGL(scale_columns_kernel, columns, dim3(64), 0, st, q.col, m, bins1);
+    Q_TRY(with_value(q.nc, ColumnCounts{}, [&](auto NC) {
+        return launch_lds<hist1_kernel<NC()>>(grid, blk, (size_t)m * bins1 * 4, st, (long long)rows, m, ldd, q.cs, q.data, q.col, bins1, q.hist1);
+    }));
+    hipLaunchKernelGGL(decide1_kernel, targets, dim3(64), 0, st, m, nt, q.col, q.hist1, bins1, q.tg, (long long)rows, &q.flags->inconsistent);
+    Q_TRY(with_columns_and(q.nc, nt, TargetCounts{}, TargetCountsWide{}, [&](auto NC, auto NT) {
+        return launch_lds<hist2_kernel<NC(), NT()>>(grid, blk, (size_t)m * nt * bins2 * 4, st, (long long)rows, m, ldd, q.cs, q.data, q.col, q.tg, bins1,
+                                                     bins2, q.hist2);
+    }));
+    hipLaunchKernelGGL(decide2_kernel, targets, dim3(64), 0, st, nt, q.hist2, bins2, q.tg);
+    if (edges) {
+        hipLaunchKernelGGL(pilot_edges_kernel, dim3((unsigned)((m * nt + 63) / 64)), dim3(64), 0, st, m * nt, nt, bins2, q.col, q.tg);
         Q_TRY(hipGetLastError());
         return PEM_OK;
-    };
-
-    int path = 0;
-    bool answered = false;
-    if (plan && !use_pilot && plan->before_full)                           // (too few rows for a subsample: everything is awaited)
-        if (int rc = plan->before_full(plan->ctx, st)) return cleanup(rc);
-    if (use_pilot) {
-        // 1. the subsample's order statistics around every wanted quantile: 7 standard deviations of the subsample's rank, + 8
-        const size_t rows_p = (n + (size_t)pilot - 1) / (size_t)pilot;
-        Wanted pw{};
-        PilotEnds ends{};
-        const double n1 = n > 1 ? (double)(n - 1) : 1.0, np1 = (double)(rows_p - 1);
-        for (int q = 0; q < nq; ++q) {
-            const double p_lo = (double)rank_prev[q] / n1, p_hi = (double)rank_next[q] / n1;
-            // (the fused form: 5 -- every value inside a bracket costs a record, in the counting launch and in both passes over the
-            // records: 3.7-3.85 ms per 1e7-sample campaign with 6, 3.6 with 5, 3.5 with 4.5 on one box.  A rank outside its bracket
-            // -- 2.9e-7 per bracket end, 910 ends: one campaign in four thousand -- is noticed by the counts and costs that call the
-            // stored-profile route; PEM_FUSED_SIGMA moves it)
-            double sig = fused ? 5.0 : 7.0;
-            if (fused)
-                if (const char* e = getenv("PEM_FUSED_SIGMA")) sig = atof(e) >= 3.0 ? atof(e) : 3.0;
-            const double d_lo = sig * sqrt((double)rows_p * p_lo * (1.0 - p_lo)) + 8.0, d_hi = sig * sqrt((double)rows_p * p_hi * (1.0 - p_hi)) + 8.0;
-            const double r_lo = floor(p_lo * np1 - d_lo) - 1.0, r_hi = ceil(p_hi * np1 + d_hi) + 1.0;
-            ends.open_lo[q] = r_lo < 0.0;
-            ends.open_hi[q] = r_hi > np1;
-            pw.prev[q] = ends.open_lo[q] ? 0 : (u64)r_lo;
-            pw.next[q] = ends.open_hi[q] ? (u64)(rows_p - 1) : (u64)r_hi;
-        }
-        if (fused) {                                                        // the producer writes the pilot rows (contiguous) first
-            if (int rc = fused->pilot(rows_p, const_cast<double*>(data), st)) return cleanup(rc);
-            const bool edges = !(getenv("PEM_FUSED_PILOT_EXACT") && atoi(getenv("PEM_FUSED_PILOT_EXACT")));
-            if (int rc = four_passes(rows_p, ld, pw, edges)) return rc;
-        } else if (plan) {                                                  // the FIRST rows_p rows are the subsample; the rest is awaited
-            if (int rc = four_passes(rows_p, ld, pw)) return rc;
-            if (plan->before_full)
-                if (int rc = plan->before_full(plan->ctx, st)) return cleanup(rc);
-        } else if (int rc = four_passes(rows_p, ld * (size_t)pilot, pw)) return rc;
-        // 2. pass A over everything: below / inside counts; the ranks inside their brackets become sub-bins
-        const dim3 grid = grid_for(n);
-        Q_TRY(hipMemsetAsync(total, 0, 256, st));                           // total, outside, any_single
-        Q_TRY(hipMemsetAsync(below, 0, o_end - o_bl, st));                  // below, histA
-        hipLaunchKernelGGL(brackets_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, tg, ends, binsA, br, any_single);
-        hipLaunchKernelGGL(init_columns_kernel, dim3(cblocks), dim3(64), 0, st, col, tg, m, nq, w);
-#define Q_BRHIST_(NC_, NQ_)                                                                                                  \
-    Q_LDS((bracket_hist_kernel<NC_, NQ_>));                                                                                  \
-    hipLaunchKernelGGL((bracket_hist_kernel<NC_, NQ_>), grid, blk, ldsA, st, (long long)n, m, ld, cs, data, br, any_single, binsA, col, below, histA)
-#define Q_BRHIST(NC_) Q_BY_NQ_##NC_(Q_BRHIST_, NC_)
-        unsigned rcap = 0;
-        bool pm_launched = false;                                           // fused form: the counting launch carried the premask
-        if (!fused) {
-            Q_BY_NC(Q_BRHIST);
-        } else {
-            // brackets the producer can count against?  (one small read: nothing else has to wait for the host here)
-            hipLaunchKernelGGL(bracket_check_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, br, unfit);
-            const bool want_pm = fused->pm_q25 >= 0 && fused->pm_q25 < nq && fused->pm_q75 >= 0 && fused->pm_q75 < nq && nq <= 5 &&
-                                 fused->pm_certain && fused->pm_uncertain;
-            fused->pm_done = 0;
-            if (want_pm)
-                hipLaunchKernelGGL(premask_bounds_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, m, nq, br, fused->pm_q25, fused->pm_q75,
-                                   fused->pm_factor, pm_thr, pm_bad);
-            // (No host round trip here -- it cost every campaign 40 us of an idle GPU: whether the brackets are fit for the producer and
-            // the premask's bounds usable is read back WITH the counts, after the counting launch.  Unfit brackets -- heavy ties,
-            // overlapping percentiles -- are counted against all the same, harmlessly, and the run is then declined: the producer's
-            // launch has written every output but the percentiles by then.)
-            const bool use_pm = want_pm;
-            pm_launched = want_pm;
-            // record room per wave: the brackets hold `expected` values of the array (their ranks in the subsample say so) -- half as
-            // much again, and a few thousand for the waves that get more than their share
-            double expected = 0.0;
-            for (int q = 0; q < nq; ++q) expected += (double)(pw.next[q] - pw.prev[q] + 1) * (double)pilot * (double)m;
-            rcap = (unsigned)(1.5 * expected / (double)fused_waves) + 4096u;
-            if (const char* e = getenv("PEM_QUANTILE_RECORD_CAP")) rcap = (unsigned)atoll(e);      // (tests: force the overflow path)
-            const size_t need = (size_t)fused_waves * rcap;
-            if (rec_cap < need) {
-                if (rec_buf) (void)hipFree(rec_buf);
-                rec_buf = nullptr;
-                rec_cap = 0;
-                Q_TRY(hipMalloc(&rec_buf, need * sizeof(pem::Record)));
-                rec_cap = need;
-            }
-            pem::CountIO cio;
-            cio.br = br;
-            cio.nq = nq;
-            cio.below = reinterpret_cast<unsigned long long*>(below);
-            cio.rec = rec_buf;
-            cio.rec_count = rec_count;
-            cio.cap = rcap;
-            cio.flags = prod_flags;
-            if (use_pm) {
-                cio.premask = pm_thr;
-                cio.row_certain = fused->pm_certain;
-                cio.row_uncertain = fused->pm_uncertain;
-            }
-            if (int rc = fused->count(cio, st)) return cleanup(rc);
-            int cus = 256;
-            Q_TRY(pem::device_cus(&cus));
-            const int cells = m * nq * binsA;
-            {
-                const size_t need = (size_t)cus * cells + (size_t)cus * m * nt;
-                if (part_cap < need) {
-                    if (part_buf) (void)hipFree(part_buf);
-                    part_buf = nullptr;
-                    part_cap = 0;
-                    Q_TRY(hipMalloc(&part_buf, need * sizeof(unsigned)));
-                    part_cap = need;
-                }
-            }
-#define Q_RECHIST(NQ_)                                                                                                       \
-    do {                                                                                                                     \
-        static pem::LdsAttrOnce attr;                                                                                        \
-        Q_TRY(attr.ensure(reinterpret_cast<const void*>(record_hist_kernel<NQ_>), 148 * 1024)); /* (+ 12 KB of static tables) */ \
-        hipLaunchKernelGGL(record_hist_kernel<NQ_>, dim3((unsigned)cus), dim3(RBLOCK), (size_t)m * nq * binsA * 4, st, rec_buf, rec_count, rcap, fused_waves, \
-                           br, m * nq, binsA, part_buf);                                                                     \
-    } while (0)
-            switch (nq) {
-                case 1: Q_RECHIST(1); break;
-                case 2: Q_RECHIST(2); break;
-                case 3: Q_RECHIST(3); break;
-                case 4: Q_RECHIST(4); break;
-                case 5: Q_RECHIST(5); break;
-                default: Q_RECHIST(6); break;
-            }
-#undef Q_RECHIST
-            u64* rec_sums = total + 16;                                         // (zeroed with `total` above)
-            hipLaunchKernelGGL(record_reduce_kernel, dim3((unsigned)((cells + 63) / 64)), dim3(256), 0, st, part_buf, cus, cells, histA, rec_count, rcap,
-                               fused_waves, rec_sums);
-            hipLaunchKernelGGL(record_total_check_kernel, dim3(1), dim3(64), 0, st, rec_sums, inconsistent, prod_flags);
-        }
-        hipLaunchKernelGGL(decide_bracket_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, nt, col, br, below, histA, binsA, tg, outside);
-        hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64 * MAX_NC), 0, st, m, nt, tg, total);
-        Q_TRY(hipGetLastError());
-        u64 h_tot[2] = {0, 0};
-        int h_unfit4[4] = {0, 0, 0, 0};                                    // fused form: unfit | producer flags (2) | premask bounds unfit
-        Q_TRY(hipMemcpyAsync(h_tot, total, 2 * sizeof(u64), hipMemcpyDeviceToHost, st));
-        if (fused) Q_TRY(hipMemcpyAsync(h_unfit4, unfit, sizeof h_unfit4, hipMemcpyDeviceToHost, st));
-        Q_TRY(hipStreamSynchronize(st));
-        if (fused) fused->pm_done = (pm_launched && h_unfit4[3] == 0) ? 1 : 0;
-        if (fused && (h_unfit4[0] || (int)(h_tot[1] & 0xffffffffull) != 0 || h_unfit4[1] || h_unfit4[2])) {
-            *fused_ok = 0;                     // unfit brackets, a rank outside its bracket, record overflow, a non-finite sample
-            return cleanup(PEM_OK);
-        }
-        if ((int)(h_tot[1] & 0xffffffffull) == 0) {
-            // 3. pass B: the values of those sub-bins, then the lists as in the four-pass form
-            Q_TRY(grow_candidates(h_tot[0]));
-            u64* cand = cand_buf;
-#define Q_BRCOMPACT_(NC_, NQ_) \
-    hipLaunchKernelGGL((compact_bracket_kernel<NC_, NQ_>), grid, blk, 0, st, (long long)n, m, ld, cs, data, br, tg, cand)
-#define Q_BRCOMPACT(NC_) Q_BY_NQ_##NC_(Q_BRCOMPACT_, NC_)
-            if (!fused) {
-                Q_BY_NC(Q_BRCOMPACT);
-            } else {
-                int cus = 256;
-                Q_TRY(pem::device_cus(&cus));
-                unsigned* woff = part_buf + (size_t)cus * m * nq * binsA;
-                hipLaunchKernelGGL(record_offsets_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, nt, binsA, tg, part_buf, cus, m * nq * binsA, woff);
-#define Q_RECCOMPACT(NQ_) \
-    hipLaunchKernelGGL(record_compact_kernel<NQ_>, dim3((unsigned)cus), dim3(RBLOCK), 0, st, rec_buf, rec_count, rcap, fused_waves, br, m * nq, tg, woff, cand)
-                switch (nq) {
-                    case 1: Q_RECCOMPACT(1); break;
-                    case 2: Q_RECCOMPACT(2); break;
-                    case 3: Q_RECCOMPACT(3); break;
-                    case 4: Q_RECCOMPACT(4); break;
-                    case 5: Q_RECCOMPACT(5); break;
-                    default: Q_RECCOMPACT(6); break;
-                }
-#undef Q_RECCOMPACT
-            }
-            hipLaunchKernelGGL(select_kernel, dim3((unsigned)(m * nt)), blk, 0, st, nt, tg, cand, incomplete);
-            Q_TRY(hipGetLastError());
-            answered = true;
-            path = 1;
-        } else {
-            path = 2;
-        }
     }
-    if (!answered)
-        if (int rc = four_passes(n, ld, w)) return rc;
-    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, col, tg, w, out);
+    hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64 * MAX_NC), 0, st, m, nt, q.tg, &q.flags->counted.candidates);
+    Q_TRY(hipGetLastError());
+    u64 h_total = 0;
+    Q_TRY(hipMemcpyAsync(&h_total, &q.flags->counted.candidates, sizeof(u64), hipMemcpyDeviceToHost, st));
+    Q_TRY(hipStreamSynchronize(st));
+    Q_TRY(grow_candidates(q, h_total));
+    u64* cand = q.work->cand.ptr;
+    with_columns_and(q.nc, nt, TargetCounts{}, TargetCountsWide{}, [&](auto NC, auto NT) {
+        hipLaunchKernelGGL((compact_kernel<NC(), NT()>), grid, blk, 0, st, (long long)rows, m, ldd, q.cs, q.data, q.col, q.tg, bins1, bins2, cand);
+    });
+    hipLaunchKernelGGL(select_kernel, targets, blk, 0, st, nt, q.tg, cand, reinterpret_cast<int*>(q.flags->incomplete));
+    Q_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
+struct PilotRun {
+    size_t rows = 0;                           // of the subsample
+    Wanted pw{};                               // the subsample's ranks that bracket the wanted ones
+    PilotEnds ends{};
+    unsigned rcap = 0;                         // fused form: record room per wave
+    bool pm_launched = false;                  // fused form: the counting launch carried the premask
+    u64 candidates = 0;                        // what the counting pass found: the length of all lists ...
+    bool outside = false;                      // ... a wanted rank outside its bracket: the four passes answer
+    bool declined = false;                     // ... fused form: the run cannot be used (*fused_ok = 0)
+};
+
+// 1. the subsample's order statistics around every wanted quantile: 7 standard deviations of the subsample's rank, + 8 -- and the
+// brackets made of them
+int pilot_brackets(Selection& q, PilotRun& p) {
+    const size_t n = q.n;
+    const int m = q.m, nq = q.nq;
+    hipStream_t st = q.st;
+    p.rows = (n + (size_t)q.pilot - 1) / (size_t)q.pilot;
+    const double n1 = n > 1 ? (double)(n - 1) : 1.0, np1 = (double)(p.rows - 1);
+    for (int i = 0; i < nq; ++i) {
+        const double p_lo = (double)q.w.prev[i] / n1, p_hi = (double)q.w.next[i] / n1;
+        // (the fused form: 5 -- every value inside a bracket costs a record, in the counting launch and in both passes over the
+        // records: 3.7-3.85 ms per 1e7-sample campaign with 6, 3.6 with 5, 3.5 with 4.5 on one box.  A rank outside its bracket
+        // -- 2.9e-7 per bracket end, 910 ends: one campaign in four thousand -- is noticed by the counts and costs that call the
+        // stored-profile route; PEM_FUSED_SIGMA moves it)
+        double sig = q.fused ? 5.0 : 7.0;
+        if (q.fused)
+            if (const char* e = getenv("PEM_FUSED_SIGMA")) sig = atof(e) >= 3.0 ? atof(e) : 3.0;
+        const double d_lo = sig * sqrt((double)p.rows * p_lo * (1.0 - p_lo)) + 8.0, d_hi = sig * sqrt((double)p.rows * p_hi * (1.0 - p_hi)) + 8.0;
+        const double r_lo = floor(p_lo * np1 - d_lo) - 1.0, r_hi = ceil(p_hi * np1 + d_hi) + 1.0;
+        p.ends.open_lo[i] = r_lo < 0.0;
+        p.ends.open_hi[i] = r_hi > np1;
+        p.pw.prev[i] = p.ends.open_lo[i] ? 0 : (u64)r_lo;
+        p.pw.next[i] = p.ends.open_hi[i] ? (u64)(p.rows - 1) : (u64)r_hi;
+    }
+    if (q.fused) {                                                          // the producer writes the pilot rows (contiguous) first
+        if (int rc = q.fused->pilot(p.rows, const_cast<double*>(q.data), st)) return q.cleanup(rc);
+        const bool edges = !(getenv("PEM_FUSED_PILOT_EXACT") && atoi(getenv("PEM_FUSED_PILOT_EXACT")));
+        PEM_TRY(four_passes(q, p.rows, q.ld, p.pw, edges));
+    } else if (q.plan) {                                                    // the FIRST rows are the subsample; the rest is awaited
+        PEM_TRY(four_passes(q, p.rows, q.ld, p.pw));
+        if (q.plan->before_full)
+            if (int rc = q.plan->before_full(q.plan->ctx, st)) return q.cleanup(rc);
+    } else {
+        PEM_TRY(four_passes(q, p.rows, q.ld * (size_t)q.pilot, p.pw));
+    }
+    Q_TRY(hipMemsetAsync(q.flags, 0, 256, st));                             // the flags
+    Q_TRY(hipMemsetAsync(q.below, 0, q.counts, st));                        // below, histA (and the fused form's record counts)
+    hipLaunchKernelGGL(brackets_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, q.tg, p.ends, q.binsA, q.br, &q.flags->any_single);
+    hipLaunchKernelGGL(init_columns_kernel, dim3((m + 63) / 64), dim3(64), 0, st, q.col, q.tg, m, nq, q.w);
+    return PEM_OK;
+}
+
+// fused form, pass A: the producer counts below the brackets while it makes the array and writes the values inside them out as
+// records; their histogram inside the brackets is taken over the records
+int count_records(Selection& q, PilotRun& p) {
+    const int m = q.m, nq = q.nq, nt = q.nt, binsA = q.binsA;
+    hipStream_t st = q.st;
+    pem::FusedProducer* fused = q.fused;
+    // brackets the producer can count against?  (one small read: nothing else has to wait for the host here)
+    hipLaunchKernelGGL(bracket_check_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, q.br, &q.flags->fused.unfit);
+    const bool want_pm = fused->pm_q25 >= 0 && fused->pm_q25 < nq && fused->pm_q75 >= 0 && fused->pm_q75 < nq && nq <= 5 && fused->pm_certain &&
+                         fused->pm_uncertain;
+    fused->pm_done = 0;
+    if (want_pm)
+        hipLaunchKernelGGL(premask_bounds_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, st, m, nq, q.br, fused->pm_q25, fused->pm_q75,
+                           fused->pm_factor, q.pm_thr, &q.flags->fused.pm_bad);
+    // (No host round trip here -- it cost every campaign 40 us of an idle GPU: whether the brackets are fit for the producer and
+    // the premask's bounds usable is read back WITH the counts, after the counting launch.  Unfit brackets -- heavy ties,
+    // overlapping percentiles -- are counted against all the same, harmlessly, and the run is then declined: the producer's
+    // launch has written every output but the percentiles by then.)
+    p.pm_launched = want_pm;
+    // record room per wave: the brackets hold `expected` values of the array (their ranks in the subsample say so) -- half as
+    // much again, and a few thousand for the waves that get more than their share
+    double expected = 0.0;
+    for (int i = 0; i < nq; ++i) expected += (double)(p.pw.next[i] - p.pw.prev[i] + 1) * (double)q.pilot * (double)m;
+    p.rcap = (unsigned)(1.5 * expected / (double)q.fused_waves) + 4096u;
+    if (const char* e = getenv("PEM_QUANTILE_RECORD_CAP")) p.rcap = (unsigned)atoll(e);      // (tests: force the overflow path)
+    const size_t records = (size_t)q.fused_waves * p.rcap;
+    Q_TRY(q.work->rec.reserve(records, records));
+    pem::CountIO cio;
+    cio.br = q.br;
+    cio.nq = nq;
+    cio.below = reinterpret_cast<unsigned long long*>(q.below);
+    cio.rec = q.work->rec.ptr;
+    cio.rec_count = q.rec_count;
+    cio.cap = p.rcap;
+    cio.flags = q.flags->fused.prod_flags;
+    if (want_pm) {
+        cio.premask = q.pm_thr;
+        cio.row_certain = fused->pm_certain;
+        cio.row_uncertain = fused->pm_uncertain;
+    }
+    if (int rc = fused->count(cio, st)) return q.cleanup(rc);
+    int cus = 256;
+    Q_TRY(pem::device_cus(&cus));
+    const int cells = m * nq * binsA;
+    const size_t parts = (size_t)cus * cells + (size_t)cus * m * nt;
+    Q_TRY(q.work->part.reserve(parts, parts));
+    unsigned* part = q.work->part.ptr;
+    Q_TRY(with_value(nq, QuantileCounts{}, [&](auto NQ) {
+        // (148 KB at most: + 12 KB of static tables)
+        return launch_lds<record_hist_kernel<NQ()>, 148 * 1024>(dim3((unsigned)cus), dim3(RBLOCK), (size_t)m * nq * binsA * 4, st, q.work->rec.ptr,
+                                                                 q.rec_count, p.rcap, q.fused_waves, q.br, m * nq, binsA, part);
+    }));
+    hipLaunchKernelGGL(record_reduce_kernel, dim3((unsigned)((cells + 63) / 64)), dim3(256), 0, st, part, cus, cells, q.histA, q.rec_count, p.rcap,
+                       q.fused_waves, q.flags->rec_sums);
+    hipLaunchKernelGGL(record_total_check_kernel, dim3(1), dim3(64), 0, st, q.flags->rec_sums, &q.flags->inconsistent, q.flags->fused.prod_flags);
+    return PEM_OK;
+}
+
+// 2. pass A over everything: below / inside counts; the ranks inside their brackets become sub-bins
+int counting_pass(Selection& q, PilotRun& p) {
+    const int m = q.m, nq = q.nq, nt = q.nt, binsA = q.binsA;
+    hipStream_t st = q.st;
+    if (q.fused) {
+        PEM_TRY(count_records(q, p));
+    } else {
+        Q_TRY(with_columns_and(q.nc, nq, QuantileCounts{}, QuantileCountsWide{}, [&](auto NC, auto NQ) {
+            return launch_lds<bracket_hist_kernel<NC(), NQ()>>(stream_grid(q.n, m), dim3(QBLOCK), (size_t)m * nq * (binsA + 1) * 4, st, (long long)q.n, m,
+                                                                q.ld, q.cs, q.data, q.br, &q.flags->any_single, binsA, q.col, q.below, q.histA);
+        }));
+    }
+    hipLaunchKernelGGL(decide_bracket_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, nt, q.col, q.br, q.below, q.histA, binsA, q.tg, &q.flags->counted.outside);
+    hipLaunchKernelGGL(layout_kernel, dim3(1), dim3(64 * MAX_NC), 0, st, m, nt, q.tg, &q.flags->counted.candidates);
+    Q_TRY(hipGetLastError());
+    Flags::Counted counted = {};
+    Flags::Fused fused = {};
+    Q_TRY(hipMemcpyAsync(&counted, &q.flags->counted, sizeof counted, hipMemcpyDeviceToHost, st));
+    if (q.fused) Q_TRY(hipMemcpyAsync(&fused, &q.flags->fused, sizeof fused, hipMemcpyDeviceToHost, st));
+    Q_TRY(hipStreamSynchronize(st));
+    if (q.fused) q.fused->pm_done = (p.pm_launched && fused.pm_bad == 0) ? 1 : 0;
+    // fused form: unfit brackets, a rank outside its bracket, record overflow, a non-finite sample
+    p.declined = q.fused && (fused.unfit || counted.outside != 0 || fused.prod_flags[0] || fused.prod_flags[1]);
+    p.outside = counted.outside != 0;
+    p.candidates = counted.candidates;
+    return PEM_OK;
+}
+
+// 3. pass B: the values of those sub-bins, then the lists as in the four-pass form
+int copy_pass(Selection& q, PilotRun& p) {
+    const int m = q.m, nq = q.nq, nt = q.nt;
+    hipStream_t st = q.st;
+    Q_TRY(grow_candidates(q, p.candidates));
+    u64* cand = q.work->cand.ptr;
+    if (!q.fused) {
+        with_columns_and(q.nc, nq, QuantileCounts{}, QuantileCountsWide{}, [&](auto NC, auto NQ) {
+            hipLaunchKernelGGL((compact_bracket_kernel<NC(), NQ()>), stream_grid(q.n, m), dim3(QBLOCK), 0, st, (long long)q.n, m, q.ld, q.cs, q.data, q.br,
+                               q.tg, cand);
+        });
+    } else {
+        int cus = 256;
+        Q_TRY(pem::device_cus(&cus));
+        unsigned* part = q.work->part.ptr;
+        unsigned* woff = part + (size_t)cus * m * nq * q.binsA;
+        hipLaunchKernelGGL(record_offsets_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, st, nt, q.binsA, q.tg, part, cus, m * nq * q.binsA, woff);
+        with_value(nq, QuantileCounts{}, [&](auto NQ) {
+            hipLaunchKernelGGL(record_compact_kernel<NQ()>, dim3((unsigned)cus), dim3(RBLOCK), 0, st, q.work->rec.ptr, q.rec_count, p.rcap, q.fused_waves,
+                               q.br, m * nq, q.tg, woff, cand);
+        });
+    }
+    hipLaunchKernelGGL(select_kernel, dim3((unsigned)(m * nt)), dim3(QBLOCK), 0, st, nt, q.tg, cand, reinterpret_cast<int*>(q.flags->incomplete));
+    Q_TRY(hipGetLastError());
+    return PEM_OK;
+}
+
+// the interpolation, and what the kernels reported about their own counts
+int finish(Selection& q) {
+    const int m = q.m, nq = q.nq, nt = q.nt, path = q.path;
+    hipStream_t st = q.st;
+    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)((m * nq + 63) / 64)), dim3(64), 0, st, m, nq, q.col, q.tg, q.w, q.out);
     Q_TRY(hipGetLastError());
     u64 h_incomplete[4] = {0, 0, 0, 0};
     int h_inconsistent = 0;
-    Q_TRY(hipMemcpyAsync(h_incomplete, incomplete, sizeof h_incomplete, hipMemcpyDeviceToHost, st));
-    Q_TRY(hipMemcpyAsync(&h_inconsistent, inconsistent, sizeof(int), hipMemcpyDeviceToHost, st));
+    Q_TRY(hipMemcpyAsync(h_incomplete, q.flags->incomplete, sizeof h_incomplete, hipMemcpyDeviceToHost, st));
+    Q_TRY(hipMemcpyAsync(&h_inconsistent, &q.flags->inconsistent, sizeof(int), hipMemcpyDeviceToHost, st));
     Q_TRY(hipStreamSynchronize(st));
     if (h_inconsistent > 0)
         return pem::fail(PEM_ERR_HIP, "pem_quantiles: the histogram of column %d does not add up to its number of values (internal error; result discarded; path %d)",
@@ -1757,33 +1160,39 @@ static int quantiles_impl(size_t n, int m, const double* data, size_t ld, size_t
                          "pem_quantiles: the list of column %llu, rank %llu holds %llu values where %llu were counted (internal error; result "
                          "discarded; path %d)",
                          h_incomplete[1] / nt, h_incomplete[1] % nt, h_incomplete[2], h_incomplete[3], path);
-    if (slot == 0) g_last_path.store(path);
-    if (fused_ok) *fused_ok = 1;
-#undef Q_BRCOMPACT
-#undef Q_BRCOMPACT_
-#undef Q_BRHIST
-#undef Q_BRHIST_
-#undef Q_COMPACT
-#undef Q_COMPACT_
-#undef Q_HIST2
-#undef Q_HIST2_
-#undef Q_HIST1
-#undef Q_MINMAX
-#undef Q_BY_NQ_4
-#undef Q_BY_NQ_2
-#undef Q_BY_NQ_1
-#undef Q_BY_NT_4
-#undef Q_BY_NT_2
-#undef Q_BY_NT_1
-#undef Q_BY_NQ_ALL
-#undef Q_BY_NQ_SMALL
-#undef Q_BY_NT_ALL
-#undef Q_BY_NT_SMALL
-#undef Q_BY_NC
-#undef Q_LDS
-#undef Q_TRY
-    return cleanup(PEM_OK);
+    if (q.slot == 0) g_last_path.store(path);
+    if (q.fused_ok) *q.fused_ok = 1;
+    return q.cleanup(PEM_OK);
 }
+
+int quantiles_impl(size_t n, int m, const double* data, size_t ld, size_t cs, int nq, const uint64_t* rank_prev, const uint64_t* rank_next,
+                   const double* gamma, double* out, pem_stream_t stream, pem::FusedProducer* fused, int* fused_ok, int slot = 0,
+                   const pem::SidePlan* plan = nullptr) {
+    Selection q{n, m, data, ld, cs, nq, out, static_cast<hipStream_t>(stream), fused, fused_ok, slot, plan};
+    PEM_TRY(validate(q, rank_prev, rank_next, gamma));
+    PEM_TRY(plan_selection(q));
+    std::lock_guard<std::mutex> lock(g_qwork[slot].mu);
+    PEM_TRY(size_workspace(q));
+    bool answered = false;
+    if (plan && !q.use_pilot && plan->before_full)                          // (too few rows for a subsample: everything is awaited)
+        if (int rc = plan->before_full(plan->ctx, q.st)) return q.cleanup(rc);
+    if (q.use_pilot) {
+        PilotRun p;
+        PEM_TRY(pilot_brackets(q, p));
+        PEM_TRY(counting_pass(q, p));
+        if (p.declined) {
+            *fused_ok = 0;
+            return q.cleanup(PEM_OK);
+        }
+        if (!p.outside) PEM_TRY(copy_pass(q, p));
+        answered = !p.outside;
+        q.path = answered ? 1 : 2;
+    }
+    if (!answered) PEM_TRY(four_passes(q, n, ld, q.w));
+    return finish(q);
+}
+
+}  // namespace
 
 extern "C" int pem_quantiles_strided_f64_dev(size_t n, int m, const double* data, size_t ld, size_t cs, int nq, const uint64_t* rank_prev,
                                              const uint64_t* rank_next, const double* gamma, double* out, pem_stream_t stream) {
@@ -1805,563 +1214,3 @@ extern "C" int pem_quantiles_f64_dev(size_t n, int m, const double* data, size_t
     if (ld < (size_t)(m > 0 ? m : 0)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_quantiles: leading dimension smaller than m");
     return pem_quantiles_strided_f64_dev(n, m, data, ld, 1, nq, rank_prev, rank_next, gamma, out, stream);
 }
-
-// ---- multi-rank building blocks (one level each; hallthrusterpem_amd/percentiles.py) ---------------------------------------
-namespace {
-
-dim3 stream_grid(size_t n, int m) {
-    const long long rpw = m <= 64 ? 64 / m : 1, groups = ((long long)n + rpw - 1) / rpw;
-    long long blocks = (groups + (long long)QWAVES * UNROLL - 1) / ((long long)QWAVES * UNROLL);
-    if (blocks > 256 * 2) blocks = 256 * 2;
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned)blocks);
-}
-
-}  // namespace
-
-extern "C" int pem_key_minmax_f64_dev(size_t n, int m, const double* data, size_t ld, uint64_t* kmin, uint64_t* kmax, int32_t* has_nan,
-                                      pem_stream_t stream) {
-    if (m < 1 || m > 64 * MAX_NC) return pem::fail(PEM_ERR_INVALID_ARG, "pem_key_minmax: 1 <= m <= %d columns", 64 * MAX_NC);
-    if (ld < (size_t)m) return pem::fail(PEM_ERR_INVALID_ARG, "pem_key_minmax: leading dimension smaller than m");
-    if (!kmin || !kmax || !has_nan || (n && !data)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_key_minmax: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Column* col = nullptr;
-    HIP_TRY(hipMalloc(&col, sizeof(Column) * m));
-    Target* no_targets = nullptr;
-    hipLaunchKernelGGL(init_columns_kernel, dim3((m + 63) / 64), dim3(64), 0, st, col, no_targets, m, 0, Wanted{});
-    if (n) {
-        const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-        const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-        if (nc == 1) hipLaunchKernelGGL(minmax_kernel<1>, grid, blk, 0, st, (long long)n, m, ld, (size_t)1, data, col);
-        else if (nc == 2) hipLaunchKernelGGL(minmax_kernel<2>, grid, blk, 0, st, (long long)n, m, ld, (size_t)1, data, col);
-        else hipLaunchKernelGGL(minmax_kernel<4>, grid, blk, 0, st, (long long)n, m, ld, (size_t)1, data, col);
-    }
-    hipLaunchKernelGGL(export_minmax_kernel, dim3((m + 63) / 64), dim3(64), 0, st, col, m, (u64*)kmin, (u64*)kmax, (int*)has_nan);
-    const hipError_t e = hipGetLastError();
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(col);
-    if (e != hipSuccess) return pem::fail(PEM_ERR_HIP, "pem_key_minmax: %s", hipGetErrorString(e));
-    return PEM_OK;
-}
-
-extern "C" int pem_range_hist_f64_dev(size_t n, int m, const double* data, size_t ld, int nr, const uint64_t* klo, const uint64_t* khi,
-                                      int bins, uint32_t* hist, pem_stream_t stream) {
-    if (m < 1 || m > 64 * MAX_NC) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_hist: 1 <= m <= %d columns", 64 * MAX_NC);
-    if (nr != 1 && nr != 2 && nr != 4 && nr != 6) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_hist: 1, 2, 4 or 6 ranges per column");
-    if (bins < 1 || (long long)m * nr * bins > LDS_WORDS)
-        return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_hist: m * nr * bins must not exceed %d", LDS_WORDS);
-    if (ld < (size_t)m) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_hist: leading dimension smaller than m");
-    if (!klo || !khi || !hist || (n && !data)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_hist: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)m * nr * bins, st));
-    if (n == 0) return PEM_OK;
-    const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-    const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-    const size_t lds = (size_t)m * nr * bins * 4;
-#define R_LAUNCH(NC_, NR_)                                                                                                       \
-    do {                                                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(range_hist_kernel<NC_, NR_>),                                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                      \
-        hipLaunchKernelGGL((range_hist_kernel<NC_, NR_>), grid, blk, lds, st, (long long)n, m, ld, data, (const u64*)klo,       \
-                           (const u64*)khi, bins, (unsigned*)hist);                                                              \
-    } while (0)
-#define R_BY_NR(NC_)                       \
-    do {                                   \
-        if (nr == 1) R_LAUNCH(NC_, 1);     \
-        else if (nr == 2) R_LAUNCH(NC_, 2); \
-        else if (nr == 4) R_LAUNCH(NC_, 4); \
-        else R_LAUNCH(NC_, 6);             \
-    } while (0)
-    if (nc == 1) R_BY_NR(1);
-    else if (nc == 2) R_BY_NR(2);
-    else R_BY_NR(4);
-#undef R_BY_NR
-#undef R_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-extern "C" int pem_range_narrow_dev(int n_ranges, int bins, const uint32_t* hist, uint64_t* klo, uint64_t* khi, int64_t* resid,
-                                    pem_stream_t stream) {
-    if (n_ranges < 1 || bins < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_narrow: need ranges and bins");
-    if (!hist || !klo || !khi || !resid) return pem::fail(PEM_ERR_INVALID_ARG, "pem_range_narrow: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipLaunchKernelGGL(range_narrow_kernel, dim3((unsigned)n_ranges), dim3(64), 0, static_cast<hipStream_t>(stream), bins,
-                       (const unsigned*)hist, (u64*)klo, (u64*)khi, (long long*)resid);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-// ---- the sharded selection on the single-GPU selection's passes (round 3) -------------------------------------------------------
-// The level loop above narrows a key range by 64 bins per streaming pass: eleven passes for 1e7 x 91 values.  The single-GPU
-// selection needs four, and its two histograms ADD across ranks just as well: every rank runs the same passes over its own
-// rows, the per-column min / max and the two histograms are all-reduced between them (91 x 256 and 91 x 6 x 64 counters:
-// nothing on xGMI), every rank takes the same decisions, and what is left per wanted rank -- 1 / (bins1 bins2) of a column --
-// is copied out into fixed-length padded lists that are all-gathered and selected from by one workgroup per list.
-// hallthrusterpem_amd/percentiles.py drives the stages and restates them in numpy for the gloo rehearsal on the CPU.
-// State lives in plain caller-owned device arrays (so that the collectives can run on them):
-//   kmin / kmax [m] u64, has_nan [m] i32; hist1 [m][bins1] u32; hist2 [m][nt][bins2] u32;
-//   resid [m nt] u64 (in: the wanted 0-based ranks, rewritten to the rank inside the chosen bin, then sub-bin);
-//   bin1 / bin2 [m nt] i32; done [m nt] i32 + answer [m nt] u64 (constant columns are decided at once);
-//   cand [m nt][L] u64 padded with ~0, cursor [m nt] u32 (values a list was offered: > L means it overflowed).
-namespace {
-
-__device__ __forceinline__ Scale column_scale(u64 kmin, u64 kmax, int bins1) {      // scale_columns_kernel, per lane
-    Scale sc;
-    const u64 span = kmax >= kmin ? kmax - kmin : 0;
-    int shift = 0;
-    while ((span >> shift) >> 31) ++shift;
-    const u64 mult = (((u64)bins1) << 32) / ((span >> shift) + 1);
-    sc.lo = kmin;
-    sc.shift = shift;
-    sc.mult = mult > 0xffffffffull ? 0xffffffffu : (unsigned)mult;
-    return sc;
-}
-
-
-__global__ void qsel_init_kernel(int m, u64* kmin, u64* kmax, int* has_nan) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m) {
-        kmin[c] = ~0ull;
-        kmax[c] = 0ull;
-        has_nan[c] = 0;
-    }
-}
-
-template <int NC>
-__global__ __launch_bounds__(QBLOCK) void qsel_minmax_kernel(long long n, int m, size_t ld, const double* __restrict__ data, u64* __restrict__ kmin,
-                                                              u64* __restrict__ kmax, int* __restrict__ has_nan) {
-    const Lanes L(m, threadIdx.x & 63);
-    u64 lo[NC], hi[NC];
-    int nan[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        lo[j] = ~0ull;
-        hi[j] = 0ull;
-        nan[j] = 0;
-    }
-    stream_values<NC>(n, m, ld, data, L, [&](int j, int, double x) {
-        if (x != x) nan[j] = 1;
-        else {
-            const u64 k = key_of(x);
-            lo[j] = k < lo[j] ? k : lo[j];
-            hi[j] = k > hi[j] ? k : hi[j];
-        }
-    });
-    __shared__ u64 s_lo[64 * MAX_NC], s_hi[64 * MAX_NC];
-    __shared__ int s_nan[64 * MAX_NC];
-    for (int c = threadIdx.x; c < m; c += QBLOCK) {
-        s_lo[c] = ~0ull;
-        s_hi[c] = 0ull;
-        s_nan[c] = 0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = L.col0 + 64 * j;
-        if (L.active && c < m) {
-            if (lo[j] <= hi[j]) {
-                atomicMin(&s_lo[c], lo[j]);
-                atomicMax(&s_hi[c], hi[j]);
-            }
-            if (nan[j]) atomicOr(&s_nan[c], 1);
-        }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < m; c += QBLOCK) {
-        if (s_lo[c] <= s_hi[c]) {
-            atomicMin(&kmin[c], s_lo[c]);
-            atomicMax(&kmax[c], s_hi[c]);
-        }
-        if (s_nan[c]) atomicOr(&has_nan[c], 1);
-    }
-}
-
-template <int NC>
-__global__ __launch_bounds__(QBLOCK) void qsel_hist1_kernel(long long n, int m, size_t ld, const double* __restrict__ data, const u64* __restrict__ kmin,
-                                                             const u64* __restrict__ kmax, int bins1, unsigned* __restrict__ hist1) {
-    extern __shared__ unsigned lds_hist[];
-    for (int i = threadIdx.x; i < m * bins1; i += QBLOCK) lds_hist[i] = 0;
-    __syncthreads();
-    const Lanes L(m, threadIdx.x & 63);
-    Scale sc[NC];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = L.col0 + 64 * j;
-        const bool on = L.active && c < m;
-        sc[j] = on ? column_scale(kmin[c], kmax[c], bins1) : column_scale(1, 0, bins1);
-    }
-    stream_values<NC>(n, m, ld, data, L, [&](int j, int c, double x) {
-        if (x == x) {
-            unsigned frac;
-            atomicAdd(&lds_hist[c * bins1 + bin_of(key_of(x), sc[j], frac)], 1u);
-        }
-    });
-    __syncthreads();
-    for (int i = threadIdx.x; i < m * bins1; i += QBLOCK) {
-        const unsigned v = lds_hist[i];
-        if (v) atomicAdd(&hist1[i], v);
-    }
-}
-
-// one wave per (column, target): the bin of the (all-reduced) histogram that holds the wanted rank
-__global__ __launch_bounds__(64) void qsel_decide1_kernel(int nt, const u64* __restrict__ kmin, const u64* __restrict__ kmax,
-                                                           const unsigned* __restrict__ hist1, int bins1, u64* __restrict__ resid,
-                                                           int* __restrict__ bin1, int* __restrict__ done, u64* __restrict__ answer) {
-    const int i = blockIdx.x, lane = threadIdx.x, c = i / nt;
-    if (kmin[c] >= kmax[c]) {                 // a constant column, or one without a value (its result is NaN anyway)
-        if (lane == 0) {
-            done[i] = 1;
-            answer[i] = kmin[c];
-            bin1[i] = -1;
-        }
-        return;
-    }
-    const Found f = find_bin(hist1 + (size_t)c * bins1, bins1, resid[i], lane);
-    if (lane == 0) {
-        done[i] = 0;
-        bin1[i] = f.bin;
-        resid[i] -= f.before;
-    }
-}
-
-template <int NC, int NT>
-__global__ __launch_bounds__(QBLOCK) void qsel_hist2_kernel(long long n, int m, size_t ld, const double* __restrict__ data, const u64* __restrict__ kmin,
-                                                             const u64* __restrict__ kmax, const int* __restrict__ bin1, int bins1, int bins2,
-                                                             unsigned* __restrict__ hist2) {
-    extern __shared__ unsigned lds_hist[];
-    for (int i = threadIdx.x; i < m * NT * bins2; i += QBLOCK) lds_hist[i] = 0;
-    __syncthreads();
-    const Lanes L(m, threadIdx.x & 63);
-    Scale sc[NC];
-    int tb[NC][NT];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = L.col0 + 64 * j;
-        const bool on = L.active && c < m;
-        sc[j] = on ? column_scale(kmin[c], kmax[c], bins1) : column_scale(1, 0, bins1);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            // targets of a column often share a bin: each DISTINCT bin is counted once, under the first target that has it
-            int b = on ? bin1[c * NT + t] : -1;
-#pragma unroll
-            for (int u = 0; u < t; ++u)
-                if (on && bin1[c * NT + u] == b) b = -1;
-            tb[j][t] = b;
-        }
-    }
-    // (no high-word test in front of the binning here, as the copy pass has: a first-level bin around the median holds 5-10 % of a
-    // column, so nearly every wave instruction has a lane inside one and the test only adds to the work: 1972 -> 2255 us for 1e7 x 91)
-    stream_values<NC>(n, m, ld, data, L, [&](int j, int c, double x) {
-        if (x == x) {
-            unsigned frac;
-            const int b = bin_of(key_of(x), sc[j], frac);
-            int hit = -1;                                   // at most one target holds a given bin (deduplicated above): one branch, not NT
-#pragma unroll
-            for (int t = 0; t < NT; ++t) hit = tb[j][t] == b ? t : hit;
-            if (hit >= 0) atomicAdd(&lds_hist[(c * NT + hit) * bins2 + subbin_of(frac, bins2)], 1u);
-        }
-    });
-    __syncthreads();
-    for (int i = threadIdx.x; i < m * NT * bins2; i += QBLOCK) {
-        const unsigned v = lds_hist[i];
-        if (v) atomicAdd(&hist2[i], v);
-    }
-}
-
-// one wave per (column, target): the sub-bin that holds the rank, from the all-reduced counts; how many of THIS rank's values
-// sit in it, from the local ones (the histogram of a bin is kept under the column's first target that has it)
-__global__ __launch_bounds__(64) void qsel_decide2_kernel(int nt, const unsigned* __restrict__ hist2, const unsigned* __restrict__ hist2_local,
-                                                           int bins2, const int* __restrict__ bin1, const int* __restrict__ done,
-                                                           u64* __restrict__ resid, int* __restrict__ bin2, u64* __restrict__ count,
-                                                           unsigned* __restrict__ count_local) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const int c = i / nt, t = i - c * nt;
-    if (done[i]) {
-        if (lane == 0) {
-            bin2[i] = -1;
-            count[i] = 0;
-            count_local[i] = 0;
-        }
-        return;
-    }
-    int first = t;
-    for (int u = t - 1; u >= 0; --u)
-        if (!done[c * nt + u] && bin1[c * nt + u] == bin1[i]) first = u;
-    const Found f = find_bin(hist2 + (size_t)(c * nt + first) * bins2, bins2, resid[i], lane);
-    if (lane == 0) {
-        bin2[i] = f.bin;
-        resid[i] -= f.before;
-        count[i] = f.count;
-        count_local[i] = hist2_local[(size_t)(c * nt + first) * bins2 + f.bin];
-    }
-}
-
-// this rank's values of every wanted (bin, sub-bin), one padded list per (column, target) -- only the first target of a column
-// with a given pair collects (the others read its list)
-template <int NC, int NT>
-__global__ __launch_bounds__(QBLOCK) void qsel_compact_kernel(long long n, int m, size_t ld, const double* __restrict__ data, const u64* __restrict__ kmin,
-                                                               const u64* __restrict__ kmax, const int* __restrict__ bin1, const int* __restrict__ bin2,
-                                                               const int* __restrict__ done, int bins1, int bins2, unsigned list_len,
-                                                               u64* __restrict__ cand, unsigned* __restrict__ cursor) {
-    // the key range of every collected (bin, sub-bin), found once per workgroup -- thread i bisects for list i -- and shared
-    // through LDS: done by every lane for its own columns, the bisections were a quarter of a 1.25e6-row shard's pass
-    __shared__ unsigned s_rloh[64 * MAX_NC * 2 * PEM_QUANTILE_MAX_Q], s_rwords[64 * MAX_NC * 2 * PEM_QUANTILE_MAX_Q];
-    for (int i = threadIdx.x; i < m * NT; i += QBLOCK) {
-        const int c = i / NT, t = i - c * NT;
-        bool own = !done[i];
-        for (int u = 0; u < t; ++u)
-            if (own && !done[c * NT + u] && bin1[c * NT + u] == bin1[i] && bin2[c * NT + u] == bin2[i]) own = false;
-        u64 klo = ~0ull, khi = 0ull;
-        if (own) keys_of_bin(column_scale(kmin[c], kmax[c], bins1), kmax[c], bins2, (long long)bin1[i] * bins2 + bin2[i], klo, khi);
-        if (klo > khi) klo = khi = ~0ull;                       // nothing to collect: a range no value's key lies in
-        s_rloh[i] = (unsigned)(klo >> 32);
-        s_rwords[i] = (unsigned)(khi >> 32) - (unsigned)(klo >> 32);
-    }
-    __syncthreads();
-    const Lanes L(m, threadIdx.x & 63);
-    Scale sc[NC];
-    int tb1[NC][NT], tb2[NC][NT];
-    unsigned rloh[NC][NT], rwords[NC][NT];                  // high words of the collected sub-bins' key ranges
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int c = L.col0 + 64 * j;
-        const bool on = L.active && c < m;
-        sc[j] = on ? column_scale(kmin[c], kmax[c], bins1) : column_scale(1, 0, bins1);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            bool own = on && !done[c * NT + t];
-#pragma unroll
-            for (int u = 0; u < t; ++u)
-                if (own && !done[c * NT + u] && bin1[c * NT + u] == bin1[c * NT + t] && bin2[c * NT + u] == bin2[c * NT + t]) own = false;
-            tb1[j][t] = own ? bin1[c * NT + t] : -1;
-            tb2[j][t] = own ? bin2[c * NT + t] : -1;
-            rloh[j][t] = on ? s_rloh[c * NT + t] : 0xffffffffu;
-            rwords[j][t] = on ? s_rwords[c * NT + t] : 0u;
-        }
-    }
-    stream_values<NC>(n, m, ld, data, L, [&](int j, int c, double x) {
-        const unsigned kh = key_high(x);
-        bool near = false;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) near |= kh - rloh[j][t] <= rwords[j][t];
-        if (near && x == x) {
-            const u64 k = key_of(x);
-            unsigned frac;
-            const int b = bin_of(k, sc[j], frac);
-            const int sb = subbin_of(frac, bins2);
-            int hit = -1;                                   // list owners have distinct (bin, sub-bin) pairs: at most one matches
-#pragma unroll
-            for (int t = 0; t < NT; ++t) hit = (tb1[j][t] == b && tb2[j][t] == sb) ? t : hit;
-            if (hit >= 0) {
-                const unsigned at = atomicAdd(&cursor[c * NT + hit], 1u);
-                if (at < list_len) cand[(size_t)(c * NT + hit) * list_len + at] = k;
-            }
-        }
-    });
-}
-
-// one workgroup per (column, target): x_(resid) of the union of every rank's list of its (bin, sub-bin)
-__global__ __launch_bounds__(QBLOCK) void qsel_select_kernel(int nt, int world, unsigned list_len, size_t rank_stride, const u64* __restrict__ gathered,
-                                                              const int* __restrict__ bin1, const int* __restrict__ bin2, const int* __restrict__ done,
-                                                              const u64* __restrict__ resid, u64* __restrict__ answer) {
-    const int i = blockIdx.x;
-    if (done[i]) return;
-    const int c = i / nt, t = i - c * nt;
-    int owner = t;
-    for (int u = t - 1; u >= 0; --u)
-        if (!done[c * nt + u] && bin1[c * nt + u] == bin1[i] && bin2[c * nt + u] == bin2[i]) owner = u;
-    const u64* base = gathered + (size_t)(c * nt + owner) * list_len;
-    const u64 r = select_from([=](u64 k) { return base[(size_t)(k / list_len) * rank_stride + (size_t)(k % list_len)]; },
-                              (u64)world * list_len, resid[i], 0xfff0000000000000ull /* key of +inf: the padding lies above it */);
-    if (threadIdx.x == 0) answer[i] = r;
-}
-
-int qsel_check(const char* who, size_t n, int m, size_t ld, const void* data) {
-    if (m < 1 || m > 64 * MAX_NC) return pem::fail(PEM_ERR_INVALID_ARG, "%s: 1 <= m <= %d columns", who, 64 * MAX_NC);
-    if (ld < (size_t)m) return pem::fail(PEM_ERR_INVALID_ARG, "%s: leading dimension smaller than m", who);
-    if (n && !data) return pem::fail(PEM_ERR_INVALID_ARG, "%s: NULL data", who);
-    return pem::check_device();
-}
-
-}  // namespace
-
-extern "C" {
-
-int pem_qsel_bins(int m, int nt, int* bins1, int* bins2) {
-    if (m < 1 || m > 64 * MAX_NC || nt < 1 || nt > 2 * PEM_QUANTILE_MAX_Q || !bins1 || !bins2)
-        return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_bins: 1 <= m <= %d, 1 <= nt <= %d", 64 * MAX_NC, 2 * PEM_QUANTILE_MAX_Q);
-    *bins1 = pow2_at_most(LDS_WORDS / m, 4096);
-    *bins2 = pow2_at_most(LDS_WORDS / (m * nt), 4096);
-    return PEM_OK;
-}
-
-int pem_qsel_minmax_f64_dev(size_t n, int m, const double* data, size_t ld, uint64_t* kmin, uint64_t* kmax, int32_t* has_nan,
-                            pem_stream_t stream) {
-    if (int rc = qsel_check("pem_qsel_minmax", n, m, ld, data)) return rc;
-    if (!kmin || !kmax || !has_nan) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_minmax: NULL array");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(qsel_init_kernel, dim3((m + 63) / 64), dim3(64), 0, st, m, (u64*)kmin, (u64*)kmax, (int*)has_nan);
-    if (n) {
-        const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-        const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-        if (nc == 1) hipLaunchKernelGGL(qsel_minmax_kernel<1>, grid, blk, 0, st, (long long)n, m, ld, data, (u64*)kmin, (u64*)kmax, (int*)has_nan);
-        else if (nc == 2) hipLaunchKernelGGL(qsel_minmax_kernel<2>, grid, blk, 0, st, (long long)n, m, ld, data, (u64*)kmin, (u64*)kmax, (int*)has_nan);
-        else hipLaunchKernelGGL(qsel_minmax_kernel<4>, grid, blk, 0, st, (long long)n, m, ld, data, (u64*)kmin, (u64*)kmax, (int*)has_nan);
-    }
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_hist1_f64_dev(size_t n, int m, const double* data, size_t ld, const uint64_t* kmin, const uint64_t* kmax, int bins1,
-                           uint32_t* hist1, pem_stream_t stream) {
-    if (int rc = qsel_check("pem_qsel_hist1", n, m, ld, data)) return rc;
-    if (!kmin || !kmax || !hist1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist1: NULL array");
-    if (bins1 < 1 || (long long)m * bins1 > LDS_WORDS) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist1: m * bins1 must not exceed %d", LDS_WORDS);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(hist1, 0, sizeof(uint32_t) * (size_t)m * bins1, st));
-    if (n == 0) return PEM_OK;
-    const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-    const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-    const size_t lds = (size_t)m * bins1 * 4;
-#define H1(NC_)                                                                                                                  \
-    do {                                                                                                                         \
-        static pem::LdsAttrOnce attr;                                                                                            \
-        HIP_TRY(attr.ensure(reinterpret_cast<const void*>(qsel_hist1_kernel<NC_>)));                                             \
-        hipLaunchKernelGGL(qsel_hist1_kernel<NC_>, grid, blk, lds, st, (long long)n, m, ld, data, (const u64*)kmin, (const u64*)kmax, \
-                           bins1, (unsigned*)hist1);                                                                             \
-    } while (0)
-    if (nc == 1) H1(1);
-    else if (nc == 2) H1(2);
-    else H1(4);
-#undef H1
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_decide1_dev(int m, int nt, const uint64_t* kmin, const uint64_t* kmax, const uint32_t* hist1, int bins1, uint64_t* resid,
-                         int32_t* bin1, int32_t* done, uint64_t* answer, pem_stream_t stream) {
-    if (m < 1 || nt < 1 || bins1 < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_decide1: need columns, targets and bins");
-    if (!kmin || !kmax || !hist1 || !resid || !bin1 || !done || !answer) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_decide1: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipLaunchKernelGGL(qsel_decide1_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, static_cast<hipStream_t>(stream), nt, (const u64*)kmin,
-                       (const u64*)kmax, (const unsigned*)hist1, bins1, (u64*)resid, (int*)bin1, (int*)done, (u64*)answer);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_hist2_f64_dev(size_t n, int m, const double* data, size_t ld, const uint64_t* kmin, const uint64_t* kmax, int nt,
-                           const int32_t* bin1, int bins1, int bins2, uint32_t* hist2, pem_stream_t stream) {
-    if (int rc = qsel_check("pem_qsel_hist2", n, m, ld, data)) return rc;
-    if (nt < 2 || nt > 2 * PEM_QUANTILE_MAX_Q || (nt & 1)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist2: 2, 4, ... %d targets per column", 2 * PEM_QUANTILE_MAX_Q);
-    if (!kmin || !kmax || !bin1 || !hist2) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist2: NULL array");
-    if (bins1 < 1 || bins2 < 1 || (long long)m * nt * bins2 > LDS_WORDS)
-        return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist2: m * nt * bins2 must not exceed %d", LDS_WORDS);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(hist2, 0, sizeof(uint32_t) * (size_t)m * nt * bins2, st));
-    if (n == 0) return PEM_OK;
-    const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-    const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-    const size_t lds = (size_t)m * nt * bins2 * 4;
-#define H2(NC_, NT_)                                                                                                               \
-    do {                                                                                                                           \
-        static pem::LdsAttrOnce attr;                                                                                              \
-        HIP_TRY(attr.ensure(reinterpret_cast<const void*>(qsel_hist2_kernel<NC_, NT_>)));                                          \
-        hipLaunchKernelGGL((qsel_hist2_kernel<NC_, NT_>), grid, blk, lds, st, (long long)n, m, ld, data, (const u64*)kmin, (const u64*)kmax, \
-                           (const int*)bin1, bins1, bins2, (unsigned*)hist2);                                                      \
-    } while (0)
-#define H2_NT(NC_)                       \
-    do {                                 \
-        if (nt == 2) H2(NC_, 2);         \
-        else if (nt == 4) H2(NC_, 4);    \
-        else if (nt == 6) H2(NC_, 6);    \
-        else if (nt == 8) H2(NC_, 8);    \
-        else if (nt == 10) H2(NC_, 10);  \
-        else H2(NC_, 12);                \
-    } while (0)
-#define H2_NT_SMALL(NC_)                 \
-    do {                                 \
-        if (nt == 2) H2(NC_, 2);         \
-        else if (nt == 4) H2(NC_, 4);    \
-        else H2(NC_, 6);                 \
-    } while (0)
-    if (nc == 4 && nt > 2 * PEM_QUANTILE_MAX_Q_WIDE) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_hist2: at most %d targets for more than 128 columns", 2 * PEM_QUANTILE_MAX_Q_WIDE);
-    if (nc == 1) H2_NT(1);
-    else if (nc == 2) H2_NT(2);
-    else H2_NT_SMALL(4);
-#undef H2_NT_SMALL
-#undef H2_NT
-#undef H2
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_decide2_dev(int m, int nt, const uint32_t* hist2, const uint32_t* hist2_local, int bins2, const int32_t* bin1, const int32_t* done,
-                         uint64_t* resid, int32_t* bin2, uint64_t* count, uint32_t* count_local, pem_stream_t stream) {
-    if (m < 1 || nt < 1 || bins2 < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_decide2: need columns, targets and bins");
-    if (!hist2 || !hist2_local || !bin1 || !done || !resid || !bin2 || !count || !count_local)
-        return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_decide2: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipLaunchKernelGGL(qsel_decide2_kernel, dim3((unsigned)(m * nt)), dim3(64), 0, static_cast<hipStream_t>(stream), nt, (const unsigned*)hist2,
-                       (const unsigned*)hist2_local, bins2, (const int*)bin1, (const int*)done, (u64*)resid, (int*)bin2, (u64*)count,
-                       (unsigned*)count_local);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_compact_f64_dev(size_t n, int m, const double* data, size_t ld, const uint64_t* kmin, const uint64_t* kmax, int nt,
-                             const int32_t* bin1, const int32_t* bin2, const int32_t* done, int bins1, int bins2, uint32_t list_len,
-                             uint64_t* cand, uint32_t* cursor, pem_stream_t stream) {
-    if (int rc = qsel_check("pem_qsel_compact", n, m, ld, data)) return rc;
-    if (nt < 2 || nt > 2 * PEM_QUANTILE_MAX_Q || (nt & 1)) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_compact: 2, 4, ... %d targets per column", 2 * PEM_QUANTILE_MAX_Q);
-    if (!kmin || !kmax || !bin1 || !bin2 || !done || !cand || !cursor || list_len < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_compact: bad arguments");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(cand, 0xff, sizeof(uint64_t) * (size_t)m * nt * list_len, st));       // padding: ~0, above every key
-    HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)m * nt, st));
-    if (n == 0) return PEM_OK;
-    const int nc = m <= 64 ? 1 : (m <= 128 ? 2 : 4);
-    const dim3 grid = stream_grid(n, m), blk(QBLOCK);
-#define CP(NC_, NT_)                                                                                                                  \
-    hipLaunchKernelGGL((qsel_compact_kernel<NC_, NT_>), grid, blk, 0, st, (long long)n, m, ld, data, (const u64*)kmin, (const u64*)kmax, \
-                       (const int*)bin1, (const int*)bin2, (const int*)done, bins1, bins2, (unsigned)list_len, (u64*)cand, (unsigned*)cursor)
-#define CP_NT(NC_)                       \
-    do {                                 \
-        if (nt == 2) CP(NC_, 2);         \
-        else if (nt == 4) CP(NC_, 4);    \
-        else if (nt == 6) CP(NC_, 6);    \
-        else if (nt == 8) CP(NC_, 8);    \
-        else if (nt == 10) CP(NC_, 10);  \
-        else CP(NC_, 12);                \
-    } while (0)
-#define CP_NT_SMALL(NC_)                 \
-    do {                                 \
-        if (nt == 2) CP(NC_, 2);         \
-        else if (nt == 4) CP(NC_, 4);    \
-        else CP(NC_, 6);                 \
-    } while (0)
-    if (nc == 4 && nt > 2 * PEM_QUANTILE_MAX_Q_WIDE) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_compact: at most %d targets for more than 128 columns", 2 * PEM_QUANTILE_MAX_Q_WIDE);
-    if (nc == 1) CP_NT(1);
-    else if (nc == 2) CP_NT(2);
-    else CP_NT_SMALL(4);
-#undef CP_NT_SMALL
-#undef CP_NT
-#undef CP
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-int pem_qsel_select_dev(int m, int nt, int world, uint32_t list_len, const uint64_t* gathered, const int32_t* bin1, const int32_t* bin2,
-                        const int32_t* done, const uint64_t* resid, uint64_t* answer, pem_stream_t stream) {
-    if (m < 1 || nt < 1 || world < 1 || list_len < 1) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_select: need columns, targets, ranks and a list length");
-    if (!gathered || !bin1 || !bin2 || !done || !resid || !answer) return pem::fail(PEM_ERR_INVALID_ARG, "pem_qsel_select: NULL array");
-    if (int rc = pem::check_device()) return rc;
-    hipLaunchKernelGGL(qsel_select_kernel, dim3((unsigned)(m * nt)), dim3(QBLOCK), 0, static_cast<hipStream_t>(stream), nt, world,
-                       (unsigned)list_len, (size_t)m * nt * list_len, (const u64*)gathered, (const int*)bin1, (const int*)bin2, (const int*)done,
-                       (const u64*)resid, (u64*)answer);
-    HIP_TRY(hipGetLastError());
-    return PEM_OK;
-}
-
-}  // extern "C"

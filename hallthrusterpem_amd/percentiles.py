@@ -6,7 +6,7 @@ order statistics per column.  With all samples on one GPU `drivers.column_percen
 values left.  Values cannot be merged across GPUs without moving them, but every product of those passes can: min / max and the
 two histograms ADD (all-reduce MIN / MAX / SUM of 91 x 256 and 91 x 6 x 64 counters), so every rank takes the same decisions,
 and what is left per wanted rank -- 1 / (bins1 bins2) of a column, a few hundred keys -- is copied into fixed-length padded
-lists, all-gathered, and selected from by one workgroup per list (`pem_qsel_*`, csrc/pem_quantile.hip).  Four passes over the
+lists, all-gathered, and selected from by one workgroup per list (`pem_qsel_*`, csrc/pem_quantile_sharded.hip).  Four passes over the
 rank's shard and ~1 MB over xGMI for a campaign of 1e7 x 91 values on 8 GPUs, instead of all-gathering 7.3 GB of profiles.
 (Rounds 1-2 narrowed a key range by 64 bins per pass instead -- eleven passes; that level loop is kept as the fallback for
 lists that do not fit their cap: heavy ties such as the 1e-20 profile of invalid samples under a wanted rank.)
@@ -22,7 +22,7 @@ import numpy as np
 
 U64 = np.uint64
 TOP = U64(1) << U64(63)
-LDS_WORDS = 36864          # csrc/pem_quantile.hip: 32-bit counters per workgroup
+LDS_WORDS = 36864          # csrc/pem_quantile_core.h: 32-bit counters per workgroup
 MAX_COLUMNS = 256          # columns per kernel call (a lane owns up to four)
 LIST_CAP = 65536           # longest padded candidate list per (column, target) and rank ...
 GATHER_CAP_BYTES = 1 << 29 # ... and the most all the ranks' lists of one pass may weigh once gathered: beyond either the level loop takes over
@@ -114,7 +114,7 @@ def _lists_fit(need: int, world: int, m: int, nt: int) -> bool:
     return need <= LIST_CAP and world * m * nt * _list_len(need) * 8 <= GATHER_CAP_BYTES
 
 
-# ---- the stages, restated in numpy (csrc/pem_quantile.hip: column_scale, bin_of, subbin_of, find_bin, qsel_*_kernel) ----------------
+# ---- the stages, restated in numpy (csrc/pem_quantile_core.h: column_scale, bin_of, subbin_of, find_bin; csrc/pem_quantile_sharded.hip: qsel_*_kernel) ----------------
 def column_scale(kmin, kmax, bins1):
     """(shift, mult) of key -> bin over [kmin, kmax] per column: d = (k - kmin) >> shift < 2^31, bin = floor(d mult / 2^32)"""
     kmin, kmax = np.asarray(kmin, dtype=U64), np.asarray(kmax, dtype=U64)

@@ -1,4 +1,5 @@
-"""pem_quantiles_f64_dev / drivers.column_percentiles (csrc/pem_quantile.hip): exact per-column percentiles over the sample axis
+"""pem_quantiles_f64_dev / drivers.column_percentiles (csrc/pem_quantile.hip; the sharded stages: csrc/pem_quantile_sharded.hip,
+csrc/pem_quantile_range.hip): exact per-column percentiles over the sample axis
 -- the p25 / p75 of the IQR masks (gen_data.py:125-174) and the 5 / 50 / 95 % bands of monte_carlo.py:363-658 -- held to
 np.percentile BIT FOR BIT (order statistics are selected, not estimated, and the interpolation is numpy's own _lerp)."""
 import numpy as np
@@ -227,16 +228,19 @@ def test_five_and_six_quantiles_share_one_selection(pilot_from):
     import torch
     from hallthrusterpem_amd import _lib
     rng = np.random.default_rng(41)
-    five, six = [25.0, 75.0, 5.0, 50.0, 95.0], [0.0, 5.0, 25.0, 50.0, 99.9, 100.0]
+    four, five, six = [0.0, 10.0, 40.0, 100.0], [25.0, 75.0, 5.0, 50.0, 95.0], [0.0, 5.0, 25.0, 50.0, 99.9, 100.0]
     for shape in ((40_000, 91), (9_000, 3), (5_000, 128), (3_000, 130), (2_000, 256), (6_000, 7, 13)):
         a = rng.lognormal(0.0, 2.0, shape)
         a[rng.random(shape[0]) < 0.3] = 1e-20                # 30 % of the rows tied at the minimum: the 5 % and 25 % brackets coincide
+        _check(a, four)
         _check(a, five)
         _check(a, six)
     pilot_from(256)                                          # the pilot form from 2^8 values on
     for shape in ((300_000, 91), (200_000, 3), (100_000, 128)):
         a = rng.lognormal(0.0, 2.0, shape) * np.where(rng.random(shape) < 0.2, -1.0, 1.0)
         a[rng.random(shape[0]) < 0.1] = 1e-20
+        _check(a, four)
+        assert _last_path() == 1
         _check(a, five)
         assert _last_path() == 1
         _check(a, six)
