@@ -810,6 +810,56 @@ def sobol_indices(n_base: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed
     return res
 
 
+def sobol_profile(n_base: int, seed: int = 0, priors=None, fixed: dict | None = None, norm: str = 'log10', design: str = 'mc',
+                  scramble: bool = True, radius: float = 1.0, n_blocks: int | None = None, device=None):
+    """First-order and total Sobol' indices of the ion current density at every one of the 91 angles of the sweep, by the Saltelli
+    design of `sobol_indices`: N (d + 2) evaluations of the coupled fp64 model for the d inputs that `fixed` does not pin, all in ONE
+    launch that forms the profiles on chip and returns only sums (`sobol_profile.profile_sums`, csrc/pem_saltelli_profile.hip).
+
+    f = log10 j_ion (norm='log10', the norm the YAML gives j_ion) or j_ion itself (norm='none') at distance `radius`.  With c_k a
+    constant per angle, the launch sums per angle (fA - c) + (fB - c), its squares, t1 = (fB - c)(fAB_j - fA), t2 = (fA - fAB_j)^2
+    and the squares of both; `sobol_profile.indices` states the estimates.  E[fAB - fA] = 0, so any c leaves S1 unbiased; c comes
+    from a pilot exactly as `sobol_indices(second_order=True)` takes its own: the same launch with no varied input and a zero
+    centre over the global base samples 0 .. min(n_base, 4096) - 1, c = row 0 / (2 n_pilot).
+    design='sobol': rows A and B from the shifted Sobol' sequence (n_base <= 2^30), as in `sobol_indices`.
+
+    Returns {'S1', 'ST', 'S1_se', 'ST_se': (91, d) tensors; 'mean', 'var', 'centre': (91,); 'GS1', 'GST': (d,), the
+    variance-weighted aggregates over the profile (Lamboni et al. 2011; Gamboa et al. 2014); 'angles': the 91-point grid; 'inputs':
+    the names of the varied inputs; 'evaluations': n_base (d + 2); 'pilot_evaluations': 2 n_pilot; 'non_physical', 'invalid': the
+    thruster filter and the invalid plume rows over the main launch's evaluations; 'design'; 'norm'}.  Where var_k == 0 the
+    indices are the division's own NaN.
+    Not provided: sharding over a process group, an fp32 model, several radii in one call, second-order indices."""
+    from . import sobol_profile as _sp
+    if design not in ('mc', 'sobol'):
+        raise ValueError(f"design must be 'mc' or 'sobol', got '{design}'")
+    if norm not in _sp.NORMS:
+        raise ValueError(f"norm must be 'log10' or 'none', got '{norm}'")
+    if int(n_base) < 1:
+        raise ValueError(f'n_base must be at least 1, got {n_base}')
+    if not radius > 0:
+        raise ValueError(f'radius must be positive, got {radius}')
+    if design == 'sobol' and n_base > sampling.SOBOL_MAX_POINTS:
+        raise ValueError(f"the Sobol' sequence has 2^30 points: n_base = {n_base}")
+    import torch
+    from .models.plume import angle_grid
+    pri = dict(sampling.PEM_V0_PRIORS if priors is None else priors)
+    for k, v in (fixed or {}).items():
+        pri[k] = sampling.Prior(sampling.UNIFORM, float(v), float(v), 'fixed')
+    d = sampling.Design(priors=pri, seed=seed)
+    varied = [i for i, k in enumerate(d.names) if k not in (fixed or {})]
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    kw = dict(norm=norm, radius=radius, n_blocks=n_blocks, method=design, scramble=scramble, device=dev)
+    n_pilot = min(int(n_base), 4096)
+    pilot, _ = _sp.profile_sums(d, [], n_pilot, None, **kw)
+    centre = pilot[0] / (2 * n_pilot)
+    sums, counts = _sp.profile_sums(d, varied, int(n_base), centre, **kw)
+    res = _sp.indices(sums, int(n_base), centre)
+    res.update({'centre': centre, 'angles': torch.as_tensor(angle_grid(), dtype=torch.float64, device=dev),
+                'inputs': [d.names[i] for i in varied], 'evaluations': int(n_base) * (len(varied) + 2), 'pilot_evaluations': 2 * n_pilot,
+                'non_physical': int(counts[0]), 'invalid': int(counts[1]), 'design': design, 'norm': norm})
+    return res
+
+
 # ------------------------------------------------------------------------------------------- rejection of plume spikes
 PLUME_INPUTS = ('P_b', 'c0', 'c1', 'c2', 'c3', 'c4', 'c5', 'sigma_cex')
 

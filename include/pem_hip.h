@@ -728,6 +728,29 @@ int pem_saltelli2_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed
                               const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
                               const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks,
                               pem_stream_t stream);
+/* First-order and total sums of the whole 91-angle j_ion profile, one launch (csrc/pem_saltelli_profile.hip): the design, rows and
+ * arguments of pem_saltelli_f64_dev / pem_saltelli_qmc_f64_dev, evaluated on A, B and AB_j -- n_base (n_varied + 2) evaluations,
+ * which `flags` counts over.  One evaluation at angle k is the reference's expression (plume.py:99-102), alpha_90 = pi/2 exactly:
+ *   t = alpha_k / a;  j_k = X1a exp(-(t1 t1)) + X2a exp(-(t2 t2)) + j_cex;  a1 <= 0 or any j_k <= 0: the whole row is 1e-20
+ * f_k = j_k (norm = 0) or log10 j_k (norm = 1).  `centre`: 91 DEVICE doubles c_k, or NULL for zeros.  n_varied may be 0 (then
+ * `varied` may be NULL).  partial[n_blocks][2 + 4 n_varied][91], one deterministic partial per workgroup:
+ *   row 0        sum (fA - c) + (fB - c)
+ *   row 1        sum (fA - c)^2 + (fB - c)^2
+ *   row 2 + 4 j  sum t1,    t1 = (fB - c) (fAB_j - fA)
+ *   row 3 + 4 j  sum t1^2
+ *   row 4 + 4 j  sum t2,    t2 = (fA - fAB_j)^2
+ *   row 5 + 4 j  sum t2^2
+ * flags[n_blocks][2]: non-physical thruster results, invalid plume rows.  n_base = 0 writes zeros.  PEM_ERR_INVALID_ARG, nothing
+ * launched: n_varied outside 0..15, norm outside {0, 1}, n_blocks < 1, radius <= 0, a NULL output, and for the Sobol' design
+ * first_index + n_base > 2^30.                                                                                            */
+int pem_saltelli_profile_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind,
+                                 const double* a, const double* b, int n_varied, const int32_t* varied, int norm,
+                                 const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags, int n_blocks,
+                                 pem_stream_t stream);
+int pem_saltelli_profile_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                                     const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                                     int norm, const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags,
+                                     int n_blocks, pem_stream_t stream);
 
 /* ---- the Sobol' study over a pressure sweep (csrc/pem_sobol_sweep.hip) --------------------------------------------------
  * scripts/pem_v0/sobol.py:46-118 (compute_indices; uqtils sobol_sa, third-party: parity UNPINNED): per QoI group only the
