@@ -144,6 +144,11 @@ SIGNATURES = {
                                                C.c_double, _dp, _dp, C.c_int, _dp]),
     'pem_saltelli_profile_qmc_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp,
                                                    C.c_double, C.c_double, _dp, _dp, C.c_int, _dp]),
+    'pem_coupled_jacobian_f64_dev': (C.c_int, [_sz, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
+    'pem_gradient_sums_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_double,
+                                            C.c_double, _dp, _dp, C.c_int, _dp]),
+    'pem_gradient_sums_qmc_f64_dev': (C.c_int, [_sz, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                                C.c_double, C.c_double, _dp, _dp, C.c_int, _dp]),
     'pem_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, _f8, _f8, _f8, _f8, _f8, C.c_int,
                                           _dp, _dp, _dp, _dp, C.c_int, _dp]),
     'pem_chain_sobol_sweep_f64_dev': (C.c_int, [C.c_int, _sz, C.c_uint64, C.c_uint64, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp,

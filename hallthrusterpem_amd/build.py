@@ -6,7 +6,7 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
-SRCS = [PKG / 'csrc' / 'pem_kernels.hip', PKG / 'csrc' / 'pem_radii.hip', PKG / 'csrc' / 'pem_stages.hip', PKG / 'csrc' / 'pem_host.hip', PKG / 'csrc' / 'pem_campaign.hip', PKG / 'csrc' / 'pem_sampler.hip', PKG / 'csrc' / 'pem_svd.hip', PKG / 'csrc' / 'pem_likelihood.hip', PKG / 'csrc' / 'pem_surrogate.hip', PKG / 'csrc' / 'pem_surrogate_fields.hip', PKG / 'csrc' / 'pem_surrogate_sobol.hip', PKG / 'csrc' / 'pem_fp32.hip', PKG / 'csrc' / 'pem_saltelli.hip', PKG / 'csrc' / 'pem_saltelli2.hip', PKG / 'csrc' / 'pem_saltelli_profile.hip', PKG / 'csrc' / 'pem_latent.hip', PKG / 'csrc' / 'pem_quantile.hip', PKG / 'csrc' / 'pem_quantile_range.hip', PKG / 'csrc' / 'pem_quantile_sharded.hip', PKG / 'csrc' / 'pem_masks.hip', PKG / 'csrc' / 'pem_sobol_sweep.hip', PKG / 'csrc' / 'pem_de.hip', PKG / 'csrc' / 'pem_nm.hip', PKG / 'csrc' / 'pem_powell.hip', PKG / 'csrc' / 'pem_direct.hip', PKG / 'csrc' / 'pem_dram.hip', PKG / 'csrc' / 'pem_ensemble.hip', PKG / 'csrc' / 'pem_tempering.hip', PKG / 'csrc' / 'pem_smc.hip', PKG / 'csrc' / 'pem_chains.hip', PKG / 'csrc' / 'pem_marginals.hip', PKG / 'csrc' / 'pem_hexbin.hip', PKG / 'csrc' / 'pem_information.hip', PKG / 'csrc' / 'pem_information_theta.hip', PKG / 'csrc' / 'pem_qmc.hip']
+SRCS = [PKG / 'csrc' / 'pem_kernels.hip', PKG / 'csrc' / 'pem_radii.hip', PKG / 'csrc' / 'pem_stages.hip', PKG / 'csrc' / 'pem_host.hip', PKG / 'csrc' / 'pem_campaign.hip', PKG / 'csrc' / 'pem_sampler.hip', PKG / 'csrc' / 'pem_svd.hip', PKG / 'csrc' / 'pem_likelihood.hip', PKG / 'csrc' / 'pem_surrogate.hip', PKG / 'csrc' / 'pem_surrogate_fields.hip', PKG / 'csrc' / 'pem_surrogate_sobol.hip', PKG / 'csrc' / 'pem_fp32.hip', PKG / 'csrc' / 'pem_saltelli.hip', PKG / 'csrc' / 'pem_saltelli2.hip', PKG / 'csrc' / 'pem_saltelli_profile.hip', PKG / 'csrc' / 'pem_jacobian.hip', PKG / 'csrc' / 'pem_latent.hip', PKG / 'csrc' / 'pem_quantile.hip', PKG / 'csrc' / 'pem_quantile_range.hip', PKG / 'csrc' / 'pem_quantile_sharded.hip', PKG / 'csrc' / 'pem_masks.hip', PKG / 'csrc' / 'pem_sobol_sweep.hip', PKG / 'csrc' / 'pem_de.hip', PKG / 'csrc' / 'pem_nm.hip', PKG / 'csrc' / 'pem_powell.hip', PKG / 'csrc' / 'pem_direct.hip', PKG / 'csrc' / 'pem_dram.hip', PKG / 'csrc' / 'pem_ensemble.hip', PKG / 'csrc' / 'pem_tempering.hip', PKG / 'csrc' / 'pem_smc.hip', PKG / 'csrc' / 'pem_chains.hip', PKG / 'csrc' / 'pem_marginals.hip', PKG / 'csrc' / 'pem_hexbin.hip', PKG / 'csrc' / 'pem_information.hip', PKG / 'csrc' / 'pem_information_theta.hip', PKG / 'csrc' / 'pem_qmc.hip']
 LIB = PKG / 'libpem_hip.so'
 DEPS = SRCS + sorted((PKG / 'csrc').glob('*.h')) + [ROOT / 'include' / 'pem_hip.h']
 

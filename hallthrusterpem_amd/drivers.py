@@ -860,6 +860,57 @@ def sobol_profile(n_base: int, seed: int = 0, priors=None, fixed: dict | None = 
     return res
 
 
+def derivative_sensitivity(n: int, seed: int = 0, qois=QOI_NAMES, priors=None, fixed: dict | None = None, design: str = 'mc',
+                           device=None):
+    """Derivative-based global sensitivity measures and the active subspace of V_cc, div_angle and T_c, the companions of
+    `sobol_indices`: N evaluations of the coupled fp64 model WITH its exact Jacobian where the Saltelli design takes N (d + 2), all
+    in ONE launch that generates the samples on chip and returns only sums (`derivatives.gradient_sums`, csrc/pem_jacobian.hip).
+
+    With g_i the derivative in the coordinate the prior of input i is stated in (x_i, or log10 x_i for a log-uniform input):
+        nu_i = E[g_i^2]        ST_i <= bound_ST_i = C_i nu_i / Var f,  C_i = (b - a)^2 / pi^2 (uniform in that coordinate), sigma^2 (normal)
+    (Sobol' & Kucherenko 2009; Lamboni et al. 2013), and the eigen-decomposition of C = E[grad f grad f^T] in standardised
+    coordinates, z_i scaled by (b - a) / 2 or sigma (Constantine 2015): 'eigenvalues' in descending order, 'eigenvectors' in columns,
+    'activity'_i = sum_k lambda_k w_ik^2.  `derivatives.measures` states every estimate.
+    The centre of the variance's sums comes from a pilot as `sobol_profile` takes its own: the same launch with no varied input over
+    the samples 0 .. min(n, 4096) - 1.  `fixed` pins inputs: they are not varied.  design='sobol': the samples are the points of the
+    shifted Sobol' sequence (n <= 2^30).
+
+    Returns {'nu', 'nu_se', 'bound_ST', 'mean_gradient', 'activity': {qoi: (d,) tensor}; 'eigenvalues': {qoi: (d,)}; 'eigenvectors',
+    'C': {qoi: (d, d)}; 'mean', 'var', 'centre': {qoi: float}; 'inputs': the names of the d varied inputs; 'evaluations': n;
+    'pilot_evaluations'; 'non_physical', 'invalid', 'skipped': counts over the n samples (a skipped sample has an f or a g that is
+    not finite and enters no sum: the estimates are over n - skipped); 'design'}.
+    Not provided: other QoIs, the j_ion profile, an fp32 model, sharding over a process group, the surrogate."""
+    from . import derivatives as _dv
+    if design not in ('mc', 'sobol'):
+        raise ValueError(f"design must be 'mc' or 'sobol', got '{design}'")
+    if int(n) < 1:
+        raise ValueError(f'n must be at least 1, got {n}')
+    if design == 'sobol' and n > sampling.SOBOL_MAX_POINTS:
+        raise ValueError(f"the Sobol' sequence has 2^30 points: n = {n}")
+    rows = [{'V_cc': 0, 'div_angle': 1, 'T_c': 2}.get(k) for k in qois]
+    if any(r is None for r in rows):
+        raise ValueError(f'derivative_sensitivity handles the scalar QoIs V_cc, div_angle, T_c; got {qois}')
+    import torch
+    pri = dict(sampling.PEM_V0_PRIORS if priors is None else priors)
+    for k, v in (fixed or {}).items():
+        pri[k] = sampling.Prior(sampling.UNIFORM, float(v), float(v), 'fixed')
+    d = sampling.Design(priors=pri, seed=seed)
+    varied = [i for i, k in enumerate(d.names) if k not in (fixed or {})]
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    n_pilot = min(int(n), 4096)
+    pilot, pc = _dv.gradient_sums(d, [], n_pilot, None, method=design, device=dev)
+    centre = pilot[0] / max(n_pilot - int(pc[2]), 1)
+    sums, counts = _dv.gradient_sums(d, varied, int(n), centre, method=design, device=dev)
+    skipped = int(counts[2])
+    res = _dv.measures(sums, int(n) - skipped, d.kind[varied], d.a[varied], d.b[varied])
+    res['mean'] = res['mean'] + centre
+    res['centre'] = centre
+    out = {key: {k: (float(val[r]) if val[r].dim() == 0 else val[r]) for k, r in zip(qois, rows)} for key, val in res.items()}
+    out.update({'inputs': [d.names[i] for i in varied], 'evaluations': int(n), 'pilot_evaluations': n_pilot, 'non_physical': int(counts[0]),
+                'invalid': int(counts[1]), 'skipped': skipped, 'design': design})
+    return out
+
+
 # ------------------------------------------------------------------------------------------- rejection of plume spikes
 PLUME_INPUTS = ('P_b', 'c0', 'c1', 'c2', 'c3', 'c4', 'c5', 'sigma_cex')
 

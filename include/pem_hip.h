@@ -752,6 +752,37 @@ int pem_saltelli_profile_qmc_f64_dev(size_t n_base, uint64_t first_index, uint64
                                      int norm, const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags,
                                      int n_blocks, pem_stream_t stream);
 
+/* ---- the model's Jacobian and the sums of a derivative-based sensitivity study (csrc/pem_jacobian.hip) --------------------
+ * The three reduced QoIs f = (V_cc, div_angle, T_c) of the coupled fp64 model and d f_q / d x_i in physical units, exact and on the
+ * branch the evaluation takes (csrc/pem_jacobian.h states the chain): V_cc clamped to 0 has a zero row and T sees no cathode input;
+ * V_cc clamped to V_a has dV_cc/dV_a = 1; a1 clipped at pi/2 has no derivative with respect to P_b, c2, c3.
+ * x: [15][n] DEVICE doubles, rows as pem_coupled_f64_dev's inputs.  varied: n_varied HOST indices 0..14 in any order (n_varied may be
+ * 0, then `varied` and `jac` may be NULL).  qoi[3][n], jac[3][n_varied][n], flags[n]: bit 0 a non-physical thruster result (T < 0 or
+ * I_B0 < 0), bit 1 an invalid plume row.  PEM_ERR_INVALID_ARG, nothing launched: n_varied outside 0..15, an index outside 0..14,
+ * radius <= 0, a NULL array with n > 0.                                                                                       */
+int pem_coupled_jacobian_f64_dev(size_t n, const double* x, int n_varied, const int32_t* varied, double torr2pa, double radius,
+                                 double* qoi, double* jac, uint8_t* flags, pem_stream_t stream);
+/* One launch: row A of the design of pem_saltelli_f64_dev / pem_saltelli_qmc_f64_dev (samples first_index .. first_index + n - 1,
+ * bit-identical to pem_sample_f64_dev / pem_sample_sobol_f64_dev), the function above on it, the gradient in the prior's own
+ * coordinate -- g_i = df/dx_i, or (x_i ln 10) df/dx_i for a PEM_DIST_LOGUNIFORM input -- and per QoI q, about the centre c_q
+ * (`centre`: 3 DEVICE doubles, or NULL for zeros), with d = n_varied, partial[n_blocks][2 + 2 d + d (d + 1) / 2][3]:
+ *   row 0                 sum (f - c)
+ *   row 1                 sum (f - c)^2
+ *   rows 2 .. 1 + d       sum g_i
+ *   rows 2 + d .. 1 + 2d  sum g_i^4
+ *   rows 2 + 2d ..        sum g_i g_j for i <= j, the upper triangle row by row
+ * flags[n_blocks][3]: non-physical thruster results, invalid plume rows, skipped samples -- a sample with an f or a g that is not
+ * finite adds nothing to any sum.  One deterministic partial per workgroup (no floating-point atomics); n = 0 writes zeros.
+ * PEM_ERR_INVALID_ARG, nothing launched: n_varied outside 0..15, an index outside 0..14, n_blocks < 1, radius <= 0, a NULL output,
+ * an unknown distribution kind, and for the Sobol' design first_index + n > 2^30.                                           */
+int pem_gradient_sums_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint32_t stream_id, const int32_t* kind, const double* a,
+                              const double* b, int n_varied, const int32_t* varied, const double* centre, double torr2pa,
+                              double radius, double* partial, uint64_t* flags, int n_blocks, pem_stream_t stream);
+int pem_gradient_sums_qmc_f64_dev(size_t n, uint64_t first_index, uint64_t seed, uint32_t stream_id, int scramble,
+                                  const int32_t* kind, const double* a, const double* b, int n_varied, const int32_t* varied,
+                                  const double* centre, double torr2pa, double radius, double* partial, uint64_t* flags,
+                                  int n_blocks, pem_stream_t stream);
+
 /* ---- the Sobol' study over a pressure sweep (csrc/pem_sobol_sweep.hip) --------------------------------------------------
  * scripts/pem_v0/sobol.py:46-118 (compute_indices; uqtils sobol_sa, third-party: parity UNPINNED): per QoI group only the
  * exogenous inputs of the component that produces it are varied, every other input sits at a pin, at each of n_p background
