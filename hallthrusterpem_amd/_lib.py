@@ -66,6 +66,8 @@ SIGNATURES = {
     'pem_thruster_filter_f64_dev': (C.c_int, [_sz, C.c_int, _dp, _dp, _f8, C.c_int, _dp, _dp, _dp, _dp]),
     'pem_coupled_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [_dp] * 7 + [_dp]),
     'pem_coupled_f64': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [_dp] * 7),
+    'pem_host_plan': (C.c_int, [C.c_int, _sz, C.c_int, C.c_int] + [C.POINTER(_sz)] * 5 + [C.POINTER(C.c_int)]),
+    'pem_host_last_regime': (C.c_int, []),
     'pem_coupled_tiled_f64_dev': (C.c_int, [_sz, _f8, _f8, _dp] + [_dp] * 7 + [_dp]),
     'pem_coupled_mixed_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [_dp] * 7 + [_dp]),
     'pem_coupled_loglik_f64_dev': (C.c_int, [_sz, _f8, _f8] + [_dp] * 15 + [C.c_int, C.c_int] + [_dp] * 4 + [_dp] * 5 + [_dp]),

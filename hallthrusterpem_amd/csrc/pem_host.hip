@@ -49,19 +49,18 @@ struct Workspace {
     }
 } g_ws;
 
-// carve 256-byte aligned arrays out of the workspace
+// carve 256-byte aligned arrays out of the workspace (base == nullptr: only measure the layout, pem_host_plan)
 struct Carver {
     unsigned char* base;
     size_t off = 0;
     explicit Carver(void* b) : base(static_cast<unsigned char*>(b)) {}
     template <class T>
     T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + off);
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
         off += (count * sizeof(T) + 255) & ~size_t(255);
         return p;
     }
 };
-size_t padded(size_t bytes) { return (bytes + 255) & ~size_t(255); }
 
 // Host <-> device movement of one chunk of a host-pointer entry point.  A chunk whose whole workspace footprint fits
 // the pinned staging buffer is moved with ONE host-to-device and ONE device-to-host copy through a pinned mirror of the
@@ -91,12 +90,116 @@ struct Stage {
 // 95-108 us (tools/latency_probe.py, interleaved; profiles/latency_r04.txt).  At 560 KB of footprint (BASELINE configs[0]: 1e4 cathode
 // samples) the kernels' reads over the link cost what the copies saved: ZC_BYTES stays below that.  PEM_ZERO_COPY=0 switches it off.
 constexpr size_t ZC_BYTES = size_t(256) << 10;
-unsigned char* host_call_base(size_t footprint) {          // where a host-pointer call carves its arrays: g_ws.mu held, g_ws reserved
+bool zero_copy_enabled() {
     static const bool on = !(getenv("PEM_ZERO_COPY") && atoi(getenv("PEM_ZERO_COPY")) == 0);
-    if (on && footprint <= ZC_BYTES)
-        if (unsigned char* pin = g_stage.get()) return pin;
-    return static_cast<unsigned char*>(static_cast<void*>(g_ws.buf));
+    return on;
 }
+
+// The workspace layout of one chunk of each host-pointer entry point: the inputs are carved first (they end at `in_end`), the
+// outputs after them (they end at `end`).  With base == nullptr only the two offsets are computed: pem_host_plan measures the
+// very layout the entry points carve.
+struct CathodeArrays {
+    double* d[7];           // six inputs, V_cc
+    size_t in_end, end;
+    CathodeArrays(void* base, size_t chunk) {
+        Carver cv(base);
+        for (int i = 0; i < 6; ++i) d[i] = cv.take<double>(chunk);
+        in_end = cv.off;
+        d[6] = cv.take<double>(chunk);
+        end = cv.off;
+    }
+};
+struct ThrusterArrays {
+    double *in[4], *out[8];  // an output the caller does not ask for takes no room
+    size_t in_end, end;
+    ThrusterArrays(void* base, size_t chunk, const bool (&wanted)[8]) {
+        Carver cv(base);
+        for (auto& p : in) p = cv.take<double>(chunk);
+        in_end = cv.off;
+        for (int i = 0; i < 8; ++i) out[i] = wanted[i] ? cv.take<double>(chunk) : nullptr;
+        end = cv.off;
+    }
+};
+struct PlumeArrays {
+    double *d[10], *j, *div, *tc;
+    uint8_t* inv;
+    size_t in_end, end;
+    PlumeArrays(void* base, size_t chunk, size_t R) {
+        Carver cv(base);
+        for (auto& p : d) p = cv.take<double>(chunk);
+        in_end = cv.off;
+        j = cv.take<double>(chunk * NANG * R);
+        div = cv.take<double>(chunk * R);
+        tc = cv.take<double>(chunk * R);
+        inv = cv.take<uint8_t>(chunk);
+        end = cv.off;
+    }
+};
+struct CoupledArrays {
+    double *d[15], *vcc, *ib0, *T, *div, *tc, *j;
+    uint8_t* inv;
+    size_t in_end, end;
+    CoupledArrays(void* base, size_t chunk) {
+        Carver cv(base);
+        for (auto& p : d) p = cv.take<double>(chunk);
+        in_end = cv.off;
+        vcc = cv.take<double>(chunk);
+        ib0 = cv.take<double>(chunk);
+        T = cv.take<double>(chunk);
+        div = cv.take<double>(chunk);
+        tc = cv.take<double>(chunk);
+        inv = cv.take<uint8_t>(chunk);
+        j = cv.take<double>(chunk * NANG);   // last: without a profile the staged copy-back stops before it
+        end = cv.off;
+    }
+};
+
+// What a host-pointer call does, decided before it touches the device (pem_host_plan reports exactly this): the samples per
+// chunk, the workspace it reserves, where the carved inputs and outputs end, and how the chunk's data moves.
+//   regime 0  zero-copy: the reserved bytes fit ZC_BYTES and PEM_ZERO_COPY allows it -- the arrays are carved in the pinned buffer
+//   regime 1  inputs and outputs staged through the pinned mirror: the footprint fits STAGE_BYTES
+//   regime 2  only the inputs staged: they end within STAGE_BYTES, the footprint does not
+//   regime 3  array by array
+struct HostPlan {
+    size_t chunk, n_chunks, in_end, footprint, reserve;
+    int regime;
+};
+HostPlan finish_plan(size_t n, size_t chunk, size_t in_end, size_t footprint, size_t reserve) {
+    HostPlan pl{chunk, (n + chunk - 1) / chunk, in_end, footprint, reserve, 3};
+    if (zero_copy_enabled() && reserve <= ZC_BYTES) pl.regime = 0;
+    else if (footprint <= STAGE_BYTES) pl.regime = 1;
+    else if (in_end <= STAGE_BYTES) pl.regime = 2;
+    return pl;
+}
+HostPlan plan_cathode(size_t n) {
+    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
+    const CathodeArrays a(nullptr, chunk);
+    return finish_plan(n, chunk, a.in_end, a.end, a.end);
+}
+// the workspace (and with it the zero-copy decision) is sized for all eight outputs, whichever the caller asks for
+HostPlan plan_thruster(size_t n, const bool (&wanted)[8]) {
+    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
+    const bool all[8] = {true, true, true, true, true, true, true, true};
+    const ThrusterArrays a(nullptr, chunk, wanted), full(nullptr, chunk, all);
+    return finish_plan(n, chunk, a.in_end, a.end, full.end);
+}
+HostPlan plan_plume(size_t n, size_t R) {
+    size_t chunk = (size_t(1) << 28) / (NANG * R * 8);   // bound the profile chunk to ~256 MiB of device memory
+    if (chunk < 1024) chunk = 1024;
+    if (chunk > n) chunk = n;
+    chunk = (chunk + 63) & ~size_t(63);
+    const PlumeArrays a(nullptr, chunk, R);
+    return finish_plan(n, chunk, a.in_end, a.end, a.end);
+}
+HostPlan plan_coupled(size_t n) {
+    size_t chunk = (size_t(1) << 28) / (NANG * 8);
+    if (chunk > n) chunk = n;
+    chunk = (chunk + 63) & ~size_t(63);
+    const CoupledArrays a(nullptr, chunk);
+    return finish_plan(n, chunk, a.in_end, a.end, a.end);
+}
+
+thread_local int t_last_regime = -1;   // pem_host_last_regime
 
 struct Mover {
     unsigned char* ws;
@@ -108,11 +211,19 @@ struct Mover {
         size_t off, bytes;
     } outs[8];
     int nout = 0;
-    // inputs are carved first: they end at `in_end`; the outputs end at `footprint`
-    Mover(void* workspace, size_t in_end, size_t footprint)
+    // where a host-pointer call carves its arrays: g_ws.mu held, g_ws reserved
+    static unsigned char* base(const HostPlan& pl) {
+        if (pl.regime == 0)
+            if (unsigned char* p = g_stage.get()) return p;
+        return static_cast<unsigned char*>(g_ws.buf);
+    }
+    // one chunk of the planned call; without the pinned buffer every regime falls back to array-by-array copies
+    Mover(void* workspace, const HostPlan& pl)
         : ws(static_cast<unsigned char*>(workspace)),
-          pin(in_end <= STAGE_BYTES ? g_stage.get() : nullptr),
-          pin_out(footprint <= STAGE_BYTES ? pin : nullptr) {}
+          pin(pl.regime <= 2 ? g_stage.get() : nullptr),
+          pin_out(pl.regime <= 1 ? pin : nullptr) {
+        t_last_regime = pin ? pl.regime : 3;
+    }
     int in(const void* host, void* dev, size_t bytes) {
         if (!pin) {
             HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, nullptr));
@@ -175,6 +286,36 @@ int pem_synchronize(pem_stream_t stream) {
     return PEM_OK;
 }
 
+int pem_host_plan(int entry, size_t n, int n_radii, int n_optional, size_t* chunk, size_t* n_chunks, size_t* in_end,
+                  size_t* footprint, size_t* reserve, int* regime) {
+    if (!chunk || !n_chunks || !in_end || !footprint || !reserve || !regime)
+        return fail(PEM_ERR_INVALID_ARG, "pem_host_plan: NULL result pointer");
+    if (n == 0 || n_radii < 1) return fail(PEM_ERR_INVALID_ARG, "pem_host_plan: n and n_radii must be positive");
+    HostPlan pl;
+    switch (entry) {
+        case PEM_HOST_CATHODE: pl = plan_cathode(n); break;
+        case PEM_HOST_THRUSTER: {
+            if (n_optional < 0 || n_optional > 8) return fail(PEM_ERR_INVALID_ARG, "pem_host_plan: the thruster stage has 0 to 8 outputs");
+            bool wanted[8];
+            for (int i = 0; i < 8; ++i) wanted[i] = i < n_optional;   // the layout depends on their number only
+            pl = plan_thruster(n, wanted);
+            break;
+        }
+        case PEM_HOST_PLUME: pl = plan_plume(n, (size_t)n_radii); break;
+        case PEM_HOST_COUPLED: pl = plan_coupled(n); break;
+        default: return fail(PEM_ERR_INVALID_ARG, "pem_host_plan: unknown entry point %d", entry);
+    }
+    *chunk = pl.chunk;
+    *n_chunks = pl.n_chunks;
+    *in_end = pl.in_end;
+    *footprint = pl.footprint;
+    *reserve = pl.reserve;
+    *regime = pl.regime;
+    return PEM_OK;
+}
+
+int pem_host_last_regime(void) { return t_last_regime; }
+
 // =============================================================================================
 // host-pointer entry points: stage through the device workspace in chunks
 // =============================================================================================
@@ -185,18 +326,16 @@ int pem_cathode_f64(size_t n, const double* P_b, const double* V_a, const double
     if (int rc = check_device()) return rc;
     if (int rc = use_default_device()) return rc;
     std::lock_guard<std::mutex> lock(g_ws.mu);
-    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
-    if (int rc = g_ws.reserve(7 * padded(chunk * 8))) return rc;
-    unsigned char* const base = host_call_base(7 * padded(chunk * 8));
+    const HostPlan pl = plan_cathode(n);
+    const size_t chunk = pl.chunk;
+    if (int rc = g_ws.reserve(pl.reserve)) return rc;
+    unsigned char* const base = Mover::base(pl);
     const double* in[6] = {P_b, V_a, T_e, V_vac, Pstar, P_T};
+    const CathodeArrays a(base, chunk);
+    double* const* d = a.d;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[7];
-        for (int i = 0; i < 6; ++i) d[i] = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        d[6] = cv.take<double>(chunk);
-        Mover mv(base, in_end, cv.off);
+        Mover mv(base, pl);
         for (int i = 0; i < 6; ++i) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
         PEM_TRY(mv.flush_in());
         if (int rc = pem_cathode_f64_dev(m, d[0], d[1], d[2], d[3], d[4], d[5], torr2pa, d[6], nullptr)) return rc;
@@ -214,19 +353,20 @@ int pem_thruster_f64(size_t n, const double* V_a, const double* V_cc, const doub
     if (int rc = check_device()) return rc;
     if (int rc = use_default_device()) return rc;
     std::lock_guard<std::mutex> lock(g_ws.mu);
-    const size_t chunk = n < (size_t(1) << 24) ? n : (size_t(1) << 24);
-    if (int rc = g_ws.reserve(12 * padded(chunk * 8))) return rc;
-    unsigned char* const base = host_call_base(12 * padded(chunk * 8));
     const double* in[4] = {V_a, V_cc, mdot_a, a_1};
     double* out[8] = {I_B0, I_d, T, eta_c, eta_m, eta_v, eta_a, v_exh};
+    bool wanted[8];
+    for (int i = 0; i < 8; ++i) wanted[i] = out[i] != nullptr;
+    const HostPlan pl = plan_thruster(n, wanted);
+    const size_t chunk = pl.chunk;
+    if (int rc = g_ws.reserve(pl.reserve)) return rc;
+    unsigned char* const base = Mover::base(pl);
+    const ThrusterArrays a(base, chunk, wanted);
+    double* const* di = a.in;
+    double* const* dout = a.out;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double *di[4], *dout[8];
-        for (auto& p : di) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        for (int i = 0; i < 8; ++i) dout[i] = out[i] ? cv.take<double>(chunk) : nullptr;
-        Mover mv(base, in_end, cv.off);
+        Mover mv(base, pl);
         for (int i = 0; i < 4; ++i) PEM_TRY(mv.in(in[i] + off, di[i], m * 8));
         PEM_TRY(mv.flush_in());
         if (int rc = pem_thruster_f64_dev(m, di[0], di[1], di[2], di[3], dout[0], dout[1], dout[2], dout[3], dout[4],
@@ -252,26 +392,18 @@ int pem_plume_f64(size_t n, int n_radii, const double* radii, double torr2pa, co
     if (int rc = use_default_device()) return rc;
     std::lock_guard<std::mutex> lock(g_ws.mu);
     const size_t R = (size_t)n_radii;
-    // bound the profile chunk to ~256 MiB of device memory
-    size_t chunk = (size_t(1) << 28) / (NANG * R * 8);
-    if (chunk < 1024) chunk = 1024;
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) & ~size_t(63);
-    const size_t need = 10 * padded(chunk * 8) + padded(chunk * NANG * R * 8) + 2 * padded(chunk * R * 8) + padded(chunk);
-    if (int rc = g_ws.reserve(need)) return rc;
-    unsigned char* const base = host_call_base(need);
+    const HostPlan pl = plan_plume(n, R);
+    const size_t chunk = pl.chunk;
+    if (int rc = g_ws.reserve(pl.reserve)) return rc;
+    unsigned char* const base = Mover::base(pl);
     const double* in[10] = {P_b, c0, c1, c2, c3, c4, c5, sigma_cex, I_B0, T};
+    const PlumeArrays a(base, chunk, R);
+    double* const* d = a.d;
+    double *const dj = a.j, *const ddiv = a.div, *const dtc = a.tc;
+    uint8_t* const dinv = a.inv;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[10];
-        for (auto& p : d) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        double* dj = cv.take<double>(chunk * NANG * R);
-        double* ddiv = cv.take<double>(chunk * R);
-        double* dtc = cv.take<double>(chunk * R);
-        uint8_t* dinv = cv.take<uint8_t>(chunk);
-        Mover mv(base, in_end, cv.off);
+        Mover mv(base, pl);
         for (int i = 0; i < 10; ++i)
             if (in[i]) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
         PEM_TRY(mv.flush_in());
@@ -300,26 +432,17 @@ int pem_coupled_f64(size_t n, double torr2pa, double radius, const double* P_b, 
     if (int rc = check_device()) return rc;
     if (int rc = use_default_device()) return rc;
     std::lock_guard<std::mutex> lock(g_ws.mu);
-    size_t chunk = (size_t(1) << 28) / (NANG * 8);
-    if (chunk > n) chunk = n;
-    chunk = (chunk + 63) & ~size_t(63);
-    const size_t need = 20 * padded(chunk * 8) + padded(chunk * NANG * 8) + padded(chunk);
-    if (int rc = g_ws.reserve(need)) return rc;
-    unsigned char* const base = host_call_base(need);
+    const HostPlan pl = plan_coupled(n);
+    const size_t chunk = pl.chunk;
+    if (int rc = g_ws.reserve(pl.reserve)) return rc;
+    unsigned char* const base = Mover::base(pl);
+    const CoupledArrays a(base, chunk);
+    double* const* d = a.d;
+    double *const dvcc = a.vcc, *const dib0 = a.ib0, *const dT = a.T, *const ddiv = a.div, *const dtc = a.tc, *const dj = a.j;
+    uint8_t* const dinv = a.inv;
     for (size_t off = 0; off < n; off += chunk) {
         const size_t m = (n - off < chunk) ? n - off : chunk;
-        Carver cv(base);
-        double* d[15];
-        for (auto& p : d) p = cv.take<double>(chunk);
-        const size_t in_end = cv.off;
-        double* dvcc = cv.take<double>(chunk);
-        double* dib0 = cv.take<double>(chunk);
-        double* dT = cv.take<double>(chunk);
-        double* ddiv = cv.take<double>(chunk);
-        double* dtc = cv.take<double>(chunk);
-        uint8_t* dinv = cv.take<uint8_t>(chunk);
-        double* dj = cv.take<double>(chunk * NANG);   // last: without a profile the staged copy-back stops before it
-        Mover mv(base, in_end, cv.off);
+        Mover mv(base, pl);
         for (int i = 0; i < 15; ++i) PEM_TRY(mv.in(in[i] + off, d[i], m * 8));
         PEM_TRY(mv.flush_in());
         if (int rc = pem_coupled_f64_dev(m, torr2pa, radius, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9],

@@ -142,6 +142,34 @@ int pem_coupled_f64(size_t n, double torr2pa, double radius, const double* P_b, 
                     const double* sigma_cex, double* V_cc, double* I_B0, double* T, double* j_ion,
                     double* div_angle, double* T_c, uint8_t* invalid);
 
+/* ---- how the host-pointer entry points move their data ---------------------------------------------------------------
+ * pem_cathode_f64, pem_thruster_f64, pem_plume_f64 and pem_coupled_f64 cut a call into chunks of `chunk` samples and carve
+ * one chunk's arrays, each padded to 256 bytes, from a workspace: the inputs first (they end at byte `in_end`), the outputs
+ * after them (they end at `footprint`).
+ *   chunk      cathode, thruster: min(n, 2^24).  plume: max(1024, 2^28 / (91 n_radii 8)), at most n, rounded up to 64.
+ *              coupled: 2^28 / (91 * 8), at most n, rounded up to 64.
+ *   reserve    bytes of workspace the call asks for: the footprint, except that the thruster stage always asks for room for
+ *              all eight outputs while its footprint counts only the n_optional outputs that are not NULL.  n_optional is read
+ *              for PEM_HOST_THRUSTER only (0 .. 8); the optional arrays of the plume and of the coupled model keep their place.
+ *   regime     0  reserve <= 256 KiB and the environment does not say PEM_ZERO_COPY=0 (read once per process): the kernels
+ *                 work on a pinned host buffer, nothing is copied by the device
+ *              1  footprint <= 2 MiB: one copy in and one copy out through a pinned mirror of the layout
+ *              2  in_end <= 2 MiB < footprint: one copy in for the inputs, the outputs array by array
+ *              3  one copy per array
+ * pem_host_plan is pure arithmetic (no device needed) and is the code the four entry points take their chunk, layout and
+ * regime from.  Refused (PEM_ERR_INVALID_ARG): an unknown entry, n == 0, n_radii < 1 (pass 1 where there are no radii),
+ * n_optional outside 0 .. 8 for the thruster stage, a NULL result pointer.
+ * pem_host_last_regime(): the regime the last chunk of the calling thread's last host-pointer call really used, -1 before
+ * the first; a refused call leaves it alone.  It differs from the plan only when the pinned buffer could not be allocated
+ * (then 3).                                                                                                              */
+#define PEM_HOST_CATHODE 0
+#define PEM_HOST_THRUSTER 1
+#define PEM_HOST_PLUME 2
+#define PEM_HOST_COUPLED 3
+int pem_host_plan(int entry, size_t n, int n_radii, int n_optional, size_t* chunk, size_t* n_chunks, size_t* in_end,
+                  size_t* footprint, size_t* reserve, int* regime);
+int pem_host_last_regime(void);
+
 /* The same evaluation with the 15 inputs TILE-INTERLEAVED: x_tiled is [ceil(n / 64)][15][64] doubles -- for every 64-sample
  * tile of the kernel the 15 rows (order of pem_coupled_f64_dev's arguments: P_b V_a T_e V_vac Pstar P_T mdot_a a_1 c0..c5
  * sigma_cex) sit in one contiguous 7680-byte block, so a wave reads ONE block per tile instead of 512 bytes from each of 15
